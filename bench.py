@@ -23,8 +23,13 @@ are global, the rest couples across subdomain edges through halos (DESIGN.md §7
 scaling; the step time is the max over ranks.  The line reports the ranks the communicator
 itself saw (``ranks_seen``: ncclCommCount under RCCL) and the communication per FGMRES step.
 
-Prints ONE JSON line (rank 0) with the metric, the SpMV roofline of the same run (HIP
-events on the library's stream) and the CPU baseline (the oracle port, rank 0, N=1).
+Prints ONE JSON line (rank 0) with the metric and the SpMV roofline of the timed steps
+themselves (HIP events on the library's stream).  A plain run sets up, warms up, times
+``--steps`` steps and prints that line.  ``--full`` adds what takes runs of its own: the CPU
+baseline (the oracle port, rank 0, N=1), the STREAM-copy rate, the untimed Newton residual
+sequence (``--newton-seq``) and, for the coupled and continuation configs, the SpMV roofline
+launches after the timed steps.  ``--dump-outputs DIR`` writes what the last timed step handed
+to its caller (the updated state and the residual norms) as ``DIR/<name>.npy``, float64.
 """
 from __future__ import annotations
 
@@ -42,6 +47,23 @@ sys.path.insert(0, os.path.join(ROOT, "i-emic_amd"))
 
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 PMC_TAG = "r06"         # bench_data/pmc_<tag>.json: per-kernel PMC bytes and trace times of a step
+DUMP_MAX_BYTES = 64 * 10**6   # --dump-outputs: all files together
+DUMP_SEED = 20261015        # of the sample taken from outputs larger than that
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """--dump-outputs: one <path>/<name>.npy (float64) per array.  Where all together exceed
+    DUMP_MAX_BYTES every array of more than 1024 entries is cut to the same fraction of its
+    entries, a fixed sample (numpy's default_rng(DUMP_SEED), ascending indices), so that two
+    runs with the same arguments write the same entries."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.atleast_1d(np.asarray(v, dtype=np.float64)).ravel() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_MAX_BYTES and a.size > 1024:
+            keep = int(a.size * (0.98 * DUMP_MAX_BYTES / total))
+            a = a[np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, f"{name}.npy"), a)
 
 
 def pmc_table(config: str):
@@ -80,8 +102,15 @@ def parse():
     p.add_argument("--npx", type=int, default=1,
                    help="x parts of the process grid (1: latitude bands, the default: the fewest exchange "
                         "batches per FGMRES step, DESIGN.md §7; 0: the reference's Decomp2D rule)")
-    p.add_argument("--steps", type=int, default=3)
-    p.add_argument("--warmup", type=int, default=1)
+    p.add_argument("--steps", type=int, default=3, help="timed steps (at least 1)")
+    p.add_argument("--warmup", type=int, default=1, help="untimed steps before them")
+    p.add_argument("--full", action="store_true",
+                   help="also what takes runs of its own beside the timed steps: the CPU baseline, the "
+                        "STREAM-copy probe, the --newton-seq residual sequence, the roofline launches of "
+                        "the coupled and continuation configs")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write what the last timed step returned (updated state, residual norms; gathered "
+                        "from all ranks) as DIR/<name>.npy, float64, at most 64 MB in all")
     p.add_argument("--config", default="global2")
     p.add_argument("--mixing", type=int, default=1,
                    help="THCM 'Mixing' (vmix): 1 as in run/ocean/global/ocean_params.xml")
@@ -94,7 +123,7 @@ def parse():
                    help="T/S amplitude of the synthetic state (DESIGN.md: benchmark state)")
     p.add_argument("--newton-seq", type=int, default=3,
                    help="untimed Newton iterations from the benchmark state, reported as the "
-                        "residual sequence")
+                        "residual sequence (with --full)")
     p.add_argument("--tol", type=float, default=1e-8)
     p.add_argument("--krylov", type=int, default=90)
     p.add_argument("--restarts", type=int, default=20)
@@ -123,7 +152,7 @@ def parse():
                    help="skip the STREAM-copy probe (scripts/gpu_pmc.sh: its 1 GiB copies are no part of the step)")
     p.add_argument("--cold-reps", type=int, default=0,
                    help="extra SpMV launches after an Infinity Cache flush, reported apart")
-    p.add_argument("--no-cpu", action="store_true")
+    p.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline of --full")
     p.add_argument("--save-x1", default=None,
                    help="write the state after the last timed Newton step (gathered from all ranks) "
                         "and the starting state to this .npz (rank 0), for parity checks")
@@ -141,6 +170,11 @@ def parse():
     p.add_argument("--cpu-iters", type=int, default=8,
                    help="FGMRES iterations of the bounded CPU sample (--mode continuation)")
     a = p.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    if not a.full:
+        # a plain run does what ms_per_step needs and no more
+        a.no_cpu, a.no_stream, a.newton_seq = True, True, 0
     if a.dyn_iters is None:
         a.dyn_iters = 8 if a.config == "global1" else 4
     return a
@@ -458,17 +492,30 @@ def bench_continuation(args, R: Ranks):
     R.check_agree()
     rc, _, sv = recs[-1]
     its = [s.iters for s in sv]
-    # SpMV roofline of the 1-degree operator (this rank's rows): HIP events on the library
-    # stream, hot, after the timed steps
-    oc.computeJacobian()
-    sp_ms = oc.time_spmv(20)
+    if args.dump_outputs:
+        # the corrected state of the last timed step (each rank's rows, summed) and its parameter
+        x1 = R.gather_ref(ops.to_host(cont.state))
+        if R.rank == 0:
+            dump_outputs(args.dump_outputs, {"state": x1, "par": cont.par,
+                                             "norms": [cont.normRHStest, cont.normRHS]})
     from iemic import _lib
     nnz = int(_lib.lib().iemic_graph_nnz(oc._h))
-    nown = oc.layout()["own_rows"]
-    bsp = spmv_bytes(nnz, nown)
-    ell = stencil_ell_bytes(nown // 6, 104, nown)
-    achieved = bsp / (sp_ms * 1e-3) / 1e9
-    real = ell / (sp_ms * 1e-3) / 1e9
+    roofline = None
+    if args.full:
+        # SpMV roofline of the 1-degree operator (this rank's rows): HIP events on the library
+        # stream, hot, after the timed steps
+        oc.computeJacobian()
+        sp_ms = oc.time_spmv(20)
+        nown = oc.layout()["own_rows"]
+        bsp = spmv_bytes(nnz, nown)
+        ell = stencil_ell_bytes(nown // 6, 104, nown)
+        achieved = bsp / (sp_ms * 1e-3) / 1e9
+        real = ell / (sp_ms * 1e-3) / 1e9
+        roofline = {"kernel": "k_spmv7 (1-degree operator, rank 0's rows, HIP events, 20 back-to-back launches)",
+                    "bound": "hbm", "achieved": round(real, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(real / HBM_PEAK_GBS, 4), "traffic": None, "bytes_basis": "stencil_ell_bytes",
+                    "achieved_csr": round(achieved, 1), "frac_csr": round(achieved / HBM_PEAK_GBS, 4),
+                    "algorithmic_bytes": bsp, "stencil_ell_bytes": ell, "launch_us": round(sp_ms * 1e3, 2)}
     its_total = max(1, sum(its))
     out = {"metric": "1-degree continuation-step wall time (config C5: predictor + bordered Newton corrector)",
            "value": round(ms, 1), "unit": "ms/continuation-step", "steps": args.steps,
@@ -487,12 +534,7 @@ def bench_continuation(args, R: Ranks):
                             "norm_f": cont.normRHStest, "norm_rhs": cont.normRHS, "fgmres_iters": its,
                             "solve_ms": [round(s.t_total_ms, 1) for s in sv],
                             "vectors": "device (iemic_vec_*, summed over the ranks)"},
-           "roofline": {"kernel": "k_spmv7 (1-degree operator, rank 0's rows, HIP events, 20 back-to-back launches)",
-                        "bound": "hbm", "achieved": round(real, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                        "frac": round(real / HBM_PEAK_GBS, 4), "traffic": None, "bytes_basis": "stencil_ell_bytes",
-                        "achieved_csr": round(achieved, 1), "frac_csr": round(achieved / HBM_PEAK_GBS, 4),
-                        "algorithmic_bytes": bsp, "stencil_ell_bytes": ell, "launch_us": round(sp_ms * 1e3, 2)},
-           "cpu_baseline": None}
+           "roofline": roofline, "cpu_baseline": None}
     if not args.no_cpu and R.world == 1:
         out["cpu_baseline"] = cpu_continuation_sample(cfg, oc, cont, saved, its, args)
     if R.rank == 0:
@@ -588,6 +630,13 @@ def bench_coupled(args, R: Ranks):
     comm = oc.comm_stats()
     R.check_agree()
     r = recs[-1]
+    if args.dump_outputs:
+        # both models' states after the last timed step (the ocean's rows summed over the ranks,
+        # the atmosphere replicated)
+        x1 = R.gather_ref(oc.getState())
+        if R.rank == 0:
+            dump_outputs(args.dump_outputs, {"ocean_state": x1, "atmos_state": atm.getState(),
+                                             "norms": [r["norm_f0"], r["norm_f1"]]})
     seq = []
     if args.newton_seq > 0:
         oc.setState(xo)
@@ -595,14 +644,20 @@ def bench_coupled(args, R: Ranks):
         for _ in range(args.newton_seq):
             q = cm.newtonStep(allow_unconverged=True)
             seq.append({k: q[k] for k in ("norm_f0", "norm_f1", "iters", "converged") if k in q})
-    # SpMV roofline: the ocean block's k_spmv7 (HIP events on the library stream, hot)
-    from iemic import _lib
-    oc.setState(xo)
-    oc.computeJacobian()
-    sp_ms = oc.time_spmv(50)
-    nnz = int(_lib.lib().iemic_graph_nnz(oc._h))
-    bsp = spmv_bytes(nnz, cfg.nrows)
-    achieved = bsp / (sp_ms * 1e-3) / 1e9
+    roofline = None
+    if args.full:
+        # SpMV roofline: the ocean block's k_spmv7 (HIP events on the library stream, hot)
+        from iemic import _lib
+        oc.setState(xo)
+        oc.computeJacobian()
+        sp_ms = oc.time_spmv(50)
+        nnz = int(_lib.lib().iemic_graph_nnz(oc._h))
+        bsp = spmv_bytes(nnz, cfg.nrows)
+        achieved = bsp / (sp_ms * 1e-3) / 1e9
+        roofline = {"kernel": "k_spmv7 (ocean block, 4 degrees; HIP events, 50 back-to-back launches)",
+                    "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None,
+                    "algorithmic_bytes": bsp, "launch_us": round(sp_ms * 1e3, 2)}
     out = {"metric": "coupled ocean+atmosphere Newton-step wall time (config C4)",
            "value": round(ms, 3), "unit": "ms/Newton-step", "steps": args.steps,
            "warmup": args.warmup, "ms_per_step": round(ms, 3), "higher_is_better": False,
@@ -621,11 +676,7 @@ def bench_coupled(args, R: Ranks):
                       "solver": args.solver if args.solver == "FGMRES" else f"IDR({args.idr_s})",
                       "prec": "forward block Gauss-Seidel: ocean block GS, atmosphere exact"},
            "newton": {**r, "sequence": seq},
-           "roofline": {"kernel": "k_spmv7 (ocean block, 4 degrees; HIP events, 50 back-to-back launches)",
-                        "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                        "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None,
-                        "algorithmic_bytes": bsp, "launch_us": round(sp_ms * 1e3, 2)},
-           "cpu_baseline": None}
+           "roofline": roofline, "cpu_baseline": None}
     if not args.no_cpu and R.world == 1:
         from oracle import atmos_oracle as ao
         from oracle import oracle as orc
@@ -754,11 +805,13 @@ def bench_newton(args, R: Ranks):
     its_total = sum(i.solve.iters for i in infos)
     R.check_agree()
 
-    if args.save_x1:
+    if args.save_x1 or args.dump_outputs:
         # the updated state of the last timed step: each rank's owned rows, summed over ranks
         x1 = R.gather_ref(oc.getState())
-        if rank == 0:
+        if rank == 0 and args.save_x1:
             np.savez(args.save_x1, x0=x0h, x1=x1)
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"state": x1, "norms": [infos[-1].norm_f0, infos[-1].norm_f1]})
 
     # SpMV roofline: the k_spmv launches of the timed Newton steps themselves (HIP events
     # on the library stream around every SpMV inside FGMRES; at N > 1 the span includes

@@ -111,53 +111,59 @@ def test_atmos_oracle_fd_jacobian():
         assert not np.any(C[:, mask])
 
 
-@pytest.mark.parametrize("name", ["coupled_natl8", "coupled_natl8s"])
-def test_ocean_block_matches_fortran_fd(oracle_lib, name):
-    """Ocean::getBlock(atmos) (Ocean.C:1538-1667) == the derivative of the reference
-    Fortran's residual w.r.t. the inserted atmosphere T, q, albedo (and, with coupled S,
-    P) fields (forcing.F90:75-94, 162-182 are linear in them: a unit perturbation gives
-    the entry up to rounding)."""
-    if not oracle_lib.reference_available():
-        pytest.skip("reference Fortran library not built (this container only)")
+def fd_runs(name):
+    """The atmosphere restatement of a coupled fixture and the reference Fortran runs of
+    test_ocean_block_matches_fortran_fd: the fixture's fields ("base") and unit perturbations
+    of T, q, albedo at a few surface points (and of P with coupled S), keyed "<i>_<j>_<field>"."""
     c = cf.preset(name)
     g = golden(name)
-    L = cf.landmask(c)
     t, q, a, pars = atm_args(g)
-    xa = g["xa"]
     at = ao.AtmosOracle(c.n, c.m, c.xmin, c.xmax, c.ymin, c.ymax, c.periodic,
                         (landm_of(name)[c.l, 1:c.m + 1, 1:c.n + 1] != 0).astype(int),
                         Ooa=g["deps"][0], Os=g["deps"][1],
                         params={**ao.COUPLED_RUN_PARAMS,
                                 "Combined Forcing": c.start_params["Combined Forcing"]})
     at.suno_ocean = np.array(at.suno[1:])
-    Cb = at.block_to_ocean(c.l, at.surf, g["deps"], c.start_params["Combined Forcing"],
-                           c.start_params["Solar Forcing"], coupled_s=bool(c.coupled_s)).toarray()
-    x = g["synthetic_x"]
     p0 = g["atm_p"]
-    runs = {}
+    runs = {"base": dict(t=t, q=q, a=a, p=p0, pars=pars)}
     h = 1.0
     sel = [(3, 2), (5, 4)]          # a few surface points (i, j), 0-based
     for (i, j) in sel:
         for fld in ("t", "q", "a"):
             f2 = dict(t=t.copy(), q=q.copy(), a=a.copy(), p=p0.copy(), pars=pars)
             f2[fld][j * c.n + i] += h
-            runs[(i, j, fld)] = f2
+            runs[f"{i}_{j}_{fld}"] = f2
     if c.coupled_s:
         # the P anomaly column: the dimensional field moves by Pdist * eta qdim per unit
         f2 = dict(t=t, q=q, a=a, p=p0 + at.pdist * at.P.eta * at.P.qdim, pars=pars)
-        runs[(0, 0, "P")] = f2
-    keys = list(runs)
-    base = oracle_lib.run_reference(c.ref_dict(), L, c.par_list(), [x], use_landm=False,
-                                    atmos=dict(t=t, q=q, a=a, p=p0, pars=pars))
-    for k in keys:
-        r = oracle_lib.run_reference(c.ref_dict(), L, c.par_list(), [x], use_landm=False,
-                                     atmos=runs[k])
-        dF = (-r["B0"]) - (-base["B0"])
-        i, j, fld = k
+        runs["0_0_P"] = f2
+    return c, g, at, runs
+
+
+@pytest.mark.parametrize("name", ["coupled_natl8", "coupled_natl8s"])
+def test_ocean_block_matches_fortran_fd(name):
+    """Ocean::getBlock(atmos) (Ocean.C:1538-1667) == the derivative of the reference
+    Fortran's residual w.r.t. the inserted atmosphere T, q, albedo (and, with coupled S,
+    P) fields (forcing.F90:75-94, 162-182 are linear in them: a unit perturbation gives
+    the entry up to rounding).  The Fortran's right-hand sides of the base and the perturbed
+    runs at the synthetic state are recorded in tests/golden/coupled_fd.npz
+    (tests/golden/make_golden_coupled_fd.py runs the reference on fd_runs' fields)."""
+    c, g, at, runs = fd_runs(name)
+    Cb = at.block_to_ocean(c.l, at.surf, g["deps"], c.start_params["Combined Forcing"],
+                           c.start_params["Solar Forcing"], coupled_s=bool(c.coupled_s)).toarray()
+    rec = golden("coupled_fd")
+    base = rec[f"{name}__base"]
+    assert len(runs) >= 7
+    for k in runs:
+        if k == "base":
+            continue
+        dF = (-rec[f"{name}__{k}"]) - (-base)
+        i, j, fld = k.split("_")
         if fld == "P":
             col = at.rowP                   # the perturbation above is one unit of P
         else:
-            col = at.row(i, j, {"t": ao.TT, "q": ao.QQ, "a": ao.AA}[fld])
+            col = at.row(int(i), int(j), {"t": ao.TT, "q": ao.QQ, "a": ao.AA}[fld])
+        assert np.abs(Cb[:, col]).max() > 0
         np.testing.assert_allclose(dF, Cb[:, col], rtol=1e-6, atol=1e-9 * np.abs(Cb).max())
 
 

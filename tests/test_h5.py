@@ -5,10 +5,11 @@ import os
 import numpy as np
 import pytest
 
-from helpers import golden
+from helpers import GOLDEN, golden
 from iemic import h5
 
-REF_H5 = "/root/reference/test/ocean/ocean_reference.h5"
+# the reference's test/ocean/ocean_reference.h5, stored unchanged
+REF_H5 = os.path.join(GOLDEN, "ocean_reference.h5")
 
 
 def test_roundtrip(tmp_path):
@@ -34,7 +35,6 @@ def test_roundtrip(tmp_path):
     assert open(p, "rb").read(8) == b"\x89HDF\r\n\x1a\n"
 
 
-@pytest.mark.skipif(not os.path.exists(REF_H5), reason="reference tree absent (GPU box)")
 def test_reads_reference_state_file():
     """the reference's own test/ocean/ocean_reference.h5 (written by EpetraExt::HDF5):
     its state equals the byte-offset decode committed in tests/golden/gateway16.npz"""
