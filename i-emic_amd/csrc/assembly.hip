@@ -8,6 +8,8 @@
  *   formed in registers and contracted with the state in fillcolA order (matAvec,
  *   matetc.F90:147-166); no matrix is stored.
  *   forcing (forcing.F90:4-218) -> k_forcing (+ k_qint for the flux corrections).
+ *   get_salflux / get_temflux (probe.F90:200-355) behind THCM::getFluxes (THCM.C:1559-1593)
+ *   -> k_fluxes (+ k_flux_qint / k_flux_shift for the salinity correction).
  * Compiled with -ffp-contract=off: values are bit-identical to the reference.
  */
 #include <cmath>
@@ -140,6 +142,34 @@ __global__ void k_forcing(Geo g, const double* __restrict__ ftab, const double* 
     double f[NUN];
     forcing_cell(g, ftab, qcor, i, j, k, f);
     for (int v = 0; v < NUN; v++) frc[NUN * cell + v] = f[v];
+}
+
+/* the nine surface fluxes of the owned surface cells, one thread per cell, planar:
+ * out[f * n*m + (j-1)*n + (i-1)] (coalesced along i) */
+__global__ void __launch_bounds__(256) k_fluxes(Geo g, const double* __restrict__ ftab,
+                                                const double* __restrict__ x,
+                                                double* __restrict__ out, int mb)
+{
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= g.nx * mb) return;
+    const int i = g.ib0 + q % g.nx + 1, j = g.jb0 + q / g.nx + 1;
+    double fl[NFLUX];
+    flux_cell(g, ftab, x, i, j, fl);
+    const int64_t nm = (int64_t)g.n * g.m, s = (int64_t)(j - 1) * g.n + (i - 1);
+#pragma unroll
+    for (int f = 0; f < NFLUX; f++) out[f * nm + s] = fl[f];
+}
+/* corr[0] = qint(salflux) over the whole surface, the reference's sequential sum */
+__global__ void k_flux_qint(Geo g, const double* __restrict__ sal, double* __restrict__ corr)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    corr[0] = flux_qint(g, sal);
+}
+/* salflux = salflux - correction on every entry, land included (probe.F90:268) */
+__global__ void k_flux_shift(double* __restrict__ sal, const double* __restrict__ corr, int nm)
+{
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q < nm) sal[q] = sal[q] - corr[0];
 }
 
 /* block partials of sum T^2 and sum S^2 over the owned cells (fixed order) */
@@ -289,6 +319,36 @@ int compute_forcing(iemic_ctx* c)
     hipLaunchKernelGGL(k_forcing, dim3((unsigned)((c->nloc + 255) / 256)), dim3(256), 0,
                        c->stream, g, c->d_ftab.p, c->d_qcor.p, c->d_frc.p, c->nloc);
     HIP_OK(hipGetLastError());
+    return 0;
+}
+
+/* THCM::getFluxes (THCM.C:1559-1593).  Every rank computes its owned surface cells into a
+ * zeroed [9][n*m] buffer; the sum over the ranks completes the fields everywhere, so the
+ * salinity correction is the same sequential sum on every rank, whatever the decomposition */
+int surface_fluxes(iemic_ctx* c, const double* x_dev, double* out9, double* scorr)
+{
+    const int nm = c->n * c->m, mb = c->jb1 - c->jb0, ns = c->nx * mb;
+    DevBuf<double> d;
+    if (d.alloc((size_t)NFLUX * nm + 1)) {
+        set_error("surface_fluxes: out of device memory");
+        return IEMIC_ENOMEM;
+    }
+    int rc = dev_zero(c, d.p, (int64_t)NFLUX * nm + 1);
+    if (rc) return rc;
+    Geo g = c->geo();
+    hipLaunchKernelGGL(k_fluxes, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, c->stream, g,
+                       c->d_ftab.p, x_dev, d.p, mb);
+    HIP_OK(hipGetLastError());
+    if ((rc = allreduce_sum(c, d.p, NFLUX * nm))) return rc;
+    double* corr = d.p + (size_t)NFLUX * nm;
+    hipLaunchKernelGGL(k_flux_qint, dim3(1), dim3(64), 0, c->stream, g, d.p + (size_t)FX_SAL * nm, corr);
+    hipLaunchKernelGGL(k_flux_shift, dim3((unsigned)((nm + 255) / 256)), dim3(256), 0, c->stream,
+                       d.p + (size_t)FX_SAL * nm, corr, nm);
+    HIP_OK(hipGetLastError());
+    if ((rc = d2h(c, out9, d.p, sizeof(double) * NFLUX * nm))) return rc;
+    double cr = 0.0;
+    if ((rc = d2h(c, &cr, corr, sizeof(double)))) return rc;
+    *scorr = cr * (c->su.par[P_COMB] * c->su.par[P_SALT]);
     return 0;
 }
 

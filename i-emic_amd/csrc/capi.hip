@@ -82,7 +82,16 @@ extern "C" int iemic_device_count(void)
     return n;
 }
 
-Geo iemic_ctx::geo() const { return su.geo(d_landm.p, d_tab.p, d_atm.p); }
+Geo iemic_ctx::geo() const
+{
+    Geo g = su.geo(d_landm.p, d_tab.p, d_atm.p);
+    const size_t nm = (size_t)n * m;
+    g.ins_emip = ins_on[0] ? d_ins.p : nullptr;
+    g.ins_aemip = ins_on[1] ? d_ins.p + nm : nullptr;
+    g.ins_spert = ins_on[2] ? d_ins.p + 2 * nm : nullptr;
+    g.ins_tatm = ins_on[3] ? d_ins.p + 3 * nm : nullptr;
+    return g;
+}
 
 iemic_ctx::~iemic_ctx()
 {
@@ -743,6 +752,126 @@ extern "C" int iemic_integral_checks(iemic_ctx* c, double* salt_advection, doubl
     *salt_advection = sums[0];
     *salt_diffusion = sums[1];
     return 0;
+}
+
+/* ---- surface fluxes and inserted forcing fields ------------------------------------- */
+/* THCM::getFluxes (THCM.C:1559-1593; m_probe get_salflux / get_temflux, probe.F90:200-355),
+ * what Ocean::additionalExports writes (Ocean.C:1904-1929): out = [9][n*m] in the order of
+ * THCM's enum (_Sal, _QSOA, _QSOS, _Temp, _QSW, _QSH, _QLH, _QTOS, _MSI), (j, i) with i
+ * fastest; each rank writes the surface cells it owns.  scorr (THCM::scorr_): the salinity
+ * correction times COMB*SALT, the same on every rank. */
+extern "C" int iemic_get_fluxes(iemic_ctx* c, const double* x, double* out, double* scorr)
+{
+    CTX_CHECK(c);
+    if (!out || !scorr) return IEMIC_EINVAL;
+    const double* xd = c->d_x.p;
+    int rc = 0;
+    if (x) {
+        if ((rc = put_ref(c, x, c->d_tmp1.p))) return rc;
+        xd = c->d_tmp1.p;
+    }
+    const size_t nm = (size_t)c->n * c->m;
+    std::vector<double> all((size_t)NFLUX * nm);
+    if ((rc = surface_fluxes(c, xd, all.data(), scorr))) return rc;
+    for (int f = 0; f < NFLUX; f++)
+        for (int j = c->jb0; j < c->jb1; j++)
+            for (int i = c->ib0; i < c->ib1; i++) {
+                const size_t q = f * nm + (size_t)j * c->n + i;
+                out[q] = all[q];
+            }
+    return 0;
+}
+
+namespace {
+int ins_slot(char mode) { return mode == 'E' ? 0 : mode == 'A' ? 1 : mode == 'P' ? 2 : -1; }
+/* slot of iemic_ctx::d_ins <- field (null: back to the profile), then forcing again */
+int insert_field(iemic_ctx* c, int slot, const double* field, bool mask)
+{
+    const int n = c->n, m = c->m, l = c->l;
+    const size_t nm = (size_t)n * m;
+    if (!field) {
+        c->ins_on[slot] = 0;
+        return compute_forcing(c);
+    }
+    if (!c->d_ins.p) {
+        if (c->d_ins.alloc(4 * nm)) {
+            set_error("insert: out of device memory");
+            return IEMIC_ENOMEM;
+        }
+        int rc = dev_zero(c, c->d_ins.p, (int64_t)(4 * nm));
+        if (rc) return rc;
+    }
+    std::vector<double> v(field, field + nm);
+    if (mask)
+        for (int j = 1; j <= m; j++)
+            for (int i = 1; i <= n; i++)
+                v[(size_t)(j - 1) * n + (i - 1)] *= (double)(1 - c->su.landm[((size_t)l * (m + 2) + j) * (n + 2) + i]);
+    int rc = h2d(c, c->d_ins.p + slot * nm, v.data(), sizeof(double) * nm);
+    if (rc) return rc;
+    c->ins_on[slot] = 1;
+    return compute_forcing(c);
+}
+}  // namespace
+
+/* THCM::setEmip (THCM.C:1486-1514; m_inserts insert_emip / insert_adapted_emip /
+ * insert_emip_pert, inserts.F90:164-224, each masked with 1 - landm(i,j,l)): mode 'E' emip,
+ * 'A' adapted_emip, 'P' spert, as whole n*m surface fields on every rank.  From then on the
+ * forcing uses the field in place of the idealized profile (the reference's its = 0); NULL
+ * restores the profile. */
+extern "C" int iemic_set_emip(iemic_ctx* c, char mode, const double* field_nm)
+{
+    CTX_CHECK(c);
+    const int slot = ins_slot(mode);
+    if (slot < 0) {
+        set_error("iemic_set_emip: mode must be 'E', 'A' or 'P'");
+        return IEMIC_EINVAL;
+    }
+    return insert_field(c, slot, field_nm, true);
+}
+
+/* THCM::getEmip (THCM.C:1530-1556; m_probe get_emip / get_adapted_emip / get_emip_pert,
+ * probe.F90:140-197): the field the forcing uses; 'E' comes back times 1 - landm(i,j,l) */
+extern "C" int iemic_get_emip(iemic_ctx* c, char mode, double* out_nm)
+{
+    CTX_CHECK(c);
+    const int slot = ins_slot(mode);
+    if (slot < 0 || !out_nm) {
+        set_error("iemic_get_emip: mode must be 'E', 'A' or 'P'");
+        return IEMIC_EINVAL;
+    }
+    const int n = c->n, m = c->m, l = c->l;
+    const size_t nm = (size_t)n * m;
+    if (c->ins_on[slot]) {
+        int rc = d2h(c, out_nm, c->d_ins.p + slot * nm, sizeof(double) * nm);
+        if (rc) return rc;
+    } else {
+        const std::vector<double> t = c->su.forcing_tables();
+        for (int j = 1; j <= m; j++)
+            for (int i = 1; i <= n; i++) {
+                const size_t q = (size_t)(j - 1) * n + (i - 1);
+                const int lm = c->su.landm[((size_t)l * (m + 2) + j) * (n + 2) + i];
+                out_nm[q] = slot == 0 ? t[2 * (m + 2) + j] * (1 - lm) : slot == 1 ? 0.0 : t[3 * (m + 2) + q];
+            }
+    }
+    if (slot == 0)
+        for (int j = 1; j <= m; j++)
+            for (int i = 1; i <= n; i++)
+                out_nm[(size_t)(j - 1) * n + (i - 1)] *= (double)(1 - c->su.landm[((size_t)l * (m + 2) + j) * (n + 2) + i]);
+    return 0;
+}
+
+/* THCM::setTatm (THCM.C:1466-1483; m_inserts insert_tatm, inserts.F90:227-245, unmasked):
+ * the atmospheric temperature / heat flux the ocean-only forcing uses in place of the
+ * idealized profile (the reference's ite = 0); NULL restores the profile.  A context with
+ * coupled_t = 1 takes its tatm from iemic_set_atmosphere. */
+extern "C" int iemic_set_tatm(iemic_ctx* c, const double* field_nm)
+{
+    CTX_CHECK(c);
+    if (c->cfg.coupled_t) {
+        set_error("iemic_set_tatm: the context has coupled_t = 1 (tatm comes from the atmosphere)");
+        return IEMIC_EINVAL;
+    }
+    return insert_field(c, 3, field_nm, false);
 }
 
 extern "C" int iemic_jacobian(iemic_ctx* c)

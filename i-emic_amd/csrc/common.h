@@ -330,6 +330,10 @@ struct iemic_ctx {
     iemic::DevBuf<double> d_qcor;    /* qint corrections                                 */
     iemic::DevBuf<double> d_intc;    /* intcond coefficients (THCM.C:2549)               */
     iemic::DevBuf<double> d_atm;     /* coupled: tatm | qatm | albe (n*m each, surface)  */
+    /* inserted forcing fields emip | adapted_emip | spert | tatm (n*m each; allocated at the
+     * first insert) and which of them are set (Geo::ins_*, null otherwise) */
+    iemic::DevBuf<double> d_ins;
+    int ins_on[4] = {0, 0, 0, 0};
     /* state and operator */
     iemic::DevBuf<double> d_x, d_F, d_B, d_val; /* d_val: NSLOT x ncell                    */
     iemic::DevBuf<double> d_tmp1, d_tmp2, d_red;
@@ -462,6 +466,9 @@ void comm_destroy(iemic_ctx* c);
 int assemble_jacobian(iemic_ctx* c, const double* x_dev);
 int assemble_rhs(iemic_ctx* c, const double* x_dev, double* F_dev);
 int compute_forcing(iemic_ctx* c);
+/* the nine surface flux fields of the state x_dev (planar, [9][n*m], whole on every rank)
+ * and the salinity correction times gamma, on the host */
+int surface_fluxes(iemic_ctx* c, const double* x_dev, double* out9, double* scorr);
 int intcond_correction(iemic_ctx* c, const double* x_dev);
 /* krylov.hip */
 /* y = J x on the owned rows; x (ext layout) gets its halo rows exchanged first */

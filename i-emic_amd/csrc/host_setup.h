@@ -460,6 +460,8 @@ struct Setup {
         g.albed = albed;
         g.suno = tab_p + 9 * M2 + 2 * (l + 2);
         g.atm = atm_p;
+        g.qtnd = qtnd;
+        g.dqso = dqso;
         return g;
     }
 };

@@ -76,6 +76,7 @@ class Ocean {
                                      std::to_string(IEMIC_ABI_VERSION) + ")");
         check(iemic_create(&ctx_, &grid, landm.data()), "iemic_create");
         N_ = (size_t)iemic_nrows(ctx_);
+        nm_ = (size_t)grid.n * grid.m;
         state_ = std::make_shared<Vector>(N_);
         rhs_ = std::make_shared<Vector>(N_);
         sol_ = std::make_shared<Vector>(N_);
@@ -158,6 +159,39 @@ class Ocean {
         return it->second;
     }
 
+    /* ---- surface fluxes and inserted forcing fields (n*m, (j, i) with i fastest) ---- */
+    /* THCM::getFluxes (THCM.C:1559-1593): the nine fields in the order of THCM's enum
+     * (_Sal, _QSOA, _QSOS, _Temp, _QSW, _QSH, _QLH, _QTOS, _MSI) of the current state;
+     * scorr (optional): the salinity correction times COMB*SALT */
+    std::vector<std::vector<double>> getFluxes(double* scorr = nullptr)
+    {
+        const size_t nm = nm_;
+        std::vector<double> all(9 * nm, 0.0);
+        double sc = 0.0;
+        check(iemic_get_fluxes(ctx_, nullptr, all.data(), &sc), "getFluxes");
+        if (scorr) *scorr = sc;
+        std::vector<std::vector<double>> out;
+        for (int f = 0; f < 9; f++) out.emplace_back(all.begin() + f * nm, all.begin() + (f + 1) * nm);
+        return out;
+    }
+    /* THCM::setEmip / getEmip (THCM.C:1486-1514, 1530-1556): mode 'E', 'A' or 'P'; an empty
+     * field restores the idealized profile */
+    void setEmip(const std::vector<double>& field, char mode = 'E')
+    {
+        check(iemic_set_emip(ctx_, mode, field.empty() ? nullptr : field.data()), "setEmip");
+    }
+    std::vector<double> getEmip(char mode = 'E')
+    {
+        std::vector<double> out(nm_, 0.0);
+        check(iemic_get_emip(ctx_, mode, out.data()), "getEmip");
+        return out;
+    }
+    /* THCM::setTatm (THCM.C:1466-1483) */
+    void setTatm(const std::vector<double>& field)
+    {
+        check(iemic_set_tatm(ctx_, field.empty() ? nullptr : field.data()), "setTatm");
+    }
+
     /* ---- Belos settings (names of Ocean's solver ParameterList) ----------------- */
     iemic_krylov& solverParameters() { return krylov_; }
     const iemic_solve_info& lastSolve() const { return lastSolve_; }
@@ -179,7 +213,7 @@ class Ocean {
 
   private:
     iemic_ctx* ctx_ = nullptr;
-    size_t N_ = 0;
+    size_t N_ = 0, nm_ = 0;
     std::shared_ptr<Vector> state_, rhs_, sol_;
     iemic_krylov krylov_{};
     iemic_solve_info lastSolve_{};

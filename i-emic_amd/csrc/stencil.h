@@ -202,6 +202,11 @@ struct Geo {
     double dedt_s, qsnd;            /* coupled_S: nus (deltat/qdim) dqso; QSnd          */
     const double* suno;             /* suno(j), j = 0..m+1 (atmos_coef)                 */
     const double* atm;              /* tatm | qatm | albe | patm, (j-1)*n + (i-1), n*m  */
+    /* inserted forcing fields (m_inserts, inserts.F90:164-245; n*m, (j-1)*n + (i-1)): emip,
+     * adapted_emip, spert and tatm as the reference holds them once its = 0 / ite = 0 stop
+     * forcing from overwriting them.  Null: the idealized profile */
+    const double *ins_emip, *ins_aemip, *ins_spert, *ins_tatm;
+    double qtnd, dqso;              /* QTnd (usrc.F90:126); dqso of set_atmos_parameters */
 };
 
 HD int LM(const Geo& g, int i, int j, int k)
@@ -1233,7 +1238,8 @@ HD void diagB_cell(const Geo& g, int i, int j, int k, double* b)
     }
 }
 
-/* ---- forcing (forcing.F90:4-218, ocean-only idealized: iza = 2, ite = its = 1) ----
+/* ---- forcing (forcing.F90:4-218, ocean-only idealized: iza = 2, ite = its = 1; an
+ * inserted field, Geo::ins_*, takes the profile's place as with ite = 0 / its = 0) ----
  * ftab = [wfun(yv) (m+2) | temfun(y) (m+2) | salfun(y) (m+2) | spert (n*m)]          */
 HD void forcing_qint(const Geo& g, const double* ftab, double* qcor, int need_t, int need_s)
 {
@@ -1252,10 +1258,11 @@ HD void forcing_qint(const Geo& g, const double* ftab, double* qcor, int need_t,
         for (int i = 1; i <= n; i++) {
             const int lm = LM(g, i, j, l);
             const double cy = g.cos_y[j];
-            lt = temf[j] * cy * (1 - lm) + lt;
-            le = (salf[j] * (1 - lm)) * cy * (1 - lm) + le;
-            lz = 0.0 * cy * (1 - lm) + lz;
-            lp = spert[(j - 1) * n + (i - 1)] * cy * (1 - lm) + lp;
+            const int q = (j - 1) * n + (i - 1);
+            lt = (g.ins_tatm ? g.ins_tatm[q] : temf[j]) * cy * (1 - lm) + lt;
+            le = (g.ins_emip ? g.ins_emip[q] : salf[j] * (1 - lm)) * cy * (1 - lm) + le;
+            lz = (g.ins_aemip ? g.ins_aemip[q] : 0.0) * cy * (1 - lm) + lz;
+            lp = (g.ins_spert ? g.ins_spert[q] : spert[q]) * cy * (1 - lm) + lp;
             ls = cy * (1 - lm) + ls;
         }
     qcor[0] = need_t ? lt / ls : 0.0;   /* temcor         */
@@ -1275,6 +1282,7 @@ HD void forcing_cell(const Geo& g, const double* ftab, const double* qcor, int i
     const int TRES = g.tres, SRES = g.sres;
     for (int v = 0; v < NUN; v++) f[v] = 0.0;
     if (k == l) {
+        const int qs = (j - 1) * n + (i - 1);
         const double sigma = par[P_COMB] * par[P_WIND] * par[P_AL_T];
         if (j <= m - 1) {
             f[UU] = sigma * wfun_yv[j];
@@ -1291,10 +1299,10 @@ HD void forcing_cell(const Geo& g, const double* ftab, const double* qcor, int i
                                 g.Ooa * tatm + g.lvsc * g.eta_a * g.qdim_a * qatm - g.lvsc * g.eo0;
             f[TT] = QToa * (double)(1 - LM(g, i, j, l));
         } else {
-            f[TT] = etabi * (temf[j] - qcor[0]);
+            f[TT] = etabi * ((g.ins_tatm ? g.ins_tatm[qs] : temf[j]) - qcor[0]);
         }
         const double gamma = par[P_COMB] * par[P_SALT] * ((double)(1 - SRES) + SRES * par[P_BIOT]);
-        const double emip = salf[j] * (1 - LM(g, i, j, l));
+        const double emip = g.ins_emip ? g.ins_emip[qs] : salf[j] * (1 - LM(g, i, j, l));
         if (g.coupled_s) {
             /* E - P salinity flux (forcing.F90:162-182): QSoa = pQSnd (eo0 - eta qdim q - P);
              * no sea ice (msi = gsi = 0) */
@@ -1305,14 +1313,91 @@ HD void forcing_cell(const Geo& g, const double* ftab, const double* qcor, int i
             f[SS] = QSoa * (double)(1 - LM(g, i, j, l));
         } else {
             f[SS] = gamma * (1 - par[P_HMTP]) * (emip - qcor[1]) +
-                    gamma * par[P_HMTP] * (0.0 - qcor[2]) +
+                    gamma * par[P_HMTP] * ((g.ins_aemip ? g.ins_aemip[qs] : 0.0) - qcor[2]) +
                     par[P_SPER] * ((double)(1 - SRES) + SRES * par[P_BIOT]) *
-                        (spert[(j - 1) * n + (i - 1)] - qcor[3]);
+                        ((g.ins_spert ? g.ins_spert[qs] : spert[qs]) - qcor[3]);
         }
     }
     if (k <= l - 1)
         f[WW] = -par[P_COMB] * (1 - LM(g, i, j, k)) * par[P_RAYL] *
                 (par[P_LAMB] * (0.0 + 0.0) / 2. - (0.0 + 0.0) / 2.);
+}
+
+
+/* ---- surface fluxes (m_probe get_salflux / get_temflux, probe.F90:200-355) ---------
+ * The nine fields of THCM::getFluxes in the order of its enum (THCM.H _Sal .. _MSI).
+ * No sea-ice model: msi = 0, so the sea-ice fluxes and the mask are zero.  The salinity
+ * flux is returned before its qint correction (flux_qint). */
+enum { FX_SAL = 0, FX_QSOA, FX_QSOS, FX_TEMP, FX_QSW, FX_QSH, FX_QLH, FX_QTOS, FX_MSI, NFLUX };
+HD void flux_cell(const Geo& g, const double* ftab, const double* x, int i, int j, double* fl)
+{
+    const int n = g.n, m = g.m, l = g.l;
+    const double* par = g.par;
+    const double* temf = ftab + (m + 2);
+    const double* salf = ftab + 2 * (m + 2);
+    const int TRES = g.tres, SRES = g.sres;
+    const int lm = LM(g, i, j, l);
+    const int64_t q = (int64_t)(j - 1) * n + (i - 1);
+    const int64_t nm = (int64_t)n * m;
+    const double T = ts_arr(g, x, TT, i, j, l), S = ts_arr(g, x, SS, i, j, l);
+    /* m_usr's surface arrays: zero unless the atmosphere was inserted, which each insert
+     * does under its own coupling flag (inserts.F90:12-97: t and albedo with coupled_T, q
+     * with either, p with coupled_S); forcing fills tatm and emip with the profiles
+     * (forcing.F90:60-66, 113-119) unless a field was inserted */
+    const double qatm = (g.coupled_t || g.coupled_s) ? g.atm[nm + q] : 0.0;
+    const double albe = g.coupled_t ? g.atm[2 * nm + q] : 0.0;
+    const double patm = g.coupled_s ? g.atm[3 * nm + q] : 0.0;
+    const double tatm = g.coupled_t ? g.atm[q] : (g.ins_tatm ? g.ins_tatm[q] : temf[j]);
+    const double emip = g.ins_emip ? g.ins_emip[q] : salf[j] * (1 - lm);
+    /* deltat / qdim (deltat = 1; qdim 0 before set_atmos_parameters, where dqso = 0 too) */
+    const double rq = g.qdim_a != 0.0 ? 1.0 / g.qdim_a : 0.0;
+    for (int f = 0; f < NFLUX; f++) fl[f] = 0.0;
+
+    /* get_salflux: gamma = COMB*SALT (no Biot factor) */
+    const double gamma = par[P_COMB] * par[P_SALT];
+    const double pQSnd = par[P_COMB] * par[P_SALT] * g.qsnd;
+    const double QSoa = pQSnd * (g.eo0 + g.eta_a * g.qdim_a * (rq * g.dqso * T - qatm) - patm);
+    fl[FX_QSOA] = QSoa / g.qsnd * (double)(1 - 0);
+    if (gamma != 0) {
+        if (g.coupled_s)
+            fl[FX_SAL] = QSoa * (double)(1 - lm) / gamma;
+        else
+            fl[FX_SAL] = (double)(1 - lm) * ((double)(1 - SRES) + SRES * par[P_BIOT]) * emip -
+                         SRES * par[P_BIOT] * S / gamma;
+    }
+
+    /* get_temflux: ocean cells only; etabi = COMB*TEMP (no Biot factor) */
+    if (lm == OCEAN) {
+        const double etabi = par[P_COMB] * par[P_TEMP];
+        const double dedt = g.eta_a * g.qdim_a * rq * g.dqso;
+        const double dedq = -g.eta_a * g.qdim_a;
+        const double QSW = par[P_COMB] * par[P_SUNP] * g.suno[j] * (1 - g.albe0 - g.albed * albe);
+        const double QSH = g.Ooa * (T - tatm);
+        const double QLH = g.lvsc * (g.eo0 + dedt * T + dedq * qatm);
+        const double QToa = QSW - QSH - QLH;
+        fl[FX_QSW] = QSW / g.qtnd * (double)(1 - 0);
+        fl[FX_QSH] = -QSH / g.qtnd * (double)(1 - 0);
+        fl[FX_QLH] = -QLH / g.qtnd * (double)(1 - 0);
+        if (!g.coupled_t)
+            fl[FX_TEMP] = ((double)(1 - TRES) + TRES * par[P_BIOT]) * tatm - TRES * par[P_BIOT] * T / etabi;
+        else
+            fl[FX_TEMP] = (double)(1 - lm) * QToa / g.qtnd + 0.0;
+    }
+}
+/* qint of a whole n*m surface field (forcing.F90:536-548 -> THCM.C:2704-2737): the
+ * cos(y)-weighted mean over the ocean cells, summed in the reference's order */
+HD double flux_qint(const Geo& g, const double* fld)
+{
+    const int n = g.n, m = g.m, l = g.l;
+    double lf = 0.0, ls = 0.0;
+    for (int j = 1; j <= m; j++)
+        for (int i = 1; i <= n; i++) {
+            const int lm = LM(g, i, j, l);
+            const double cy = g.cos_y[j];
+            lf = fld[(j - 1) * n + (i - 1)] * cy * (1 - lm) + lf;
+            ls = cy * (1 - lm) + ls;
+        }
+    return lf / ls;
 }
 
 }  // namespace iemic

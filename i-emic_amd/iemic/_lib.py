@@ -16,7 +16,7 @@ PKG_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(PKG_DIR, "lib", os.environ.get("IEMIC_LIB", "libiemic_amd.so"))
 
 IEMIC_ENODEV = -19
-ABI_VERSION = 6             # IEMIC_ABI_VERSION of include/iemic.h this binding mirrors
+ABI_VERSION = 7             # IEMIC_ABI_VERSION of include/iemic.h this binding mirrors
 IEMIC_ENOCONV = 1           # iemic_newton_step: applied, but the solve missed its tolerance
 
 
@@ -185,6 +185,10 @@ def lib():
         "iemic_set_atmosphere": (C.c_int, [vp, PD, PD, PD, PD, PD]),
         "iemic_get_deps": (C.c_int, [vp, PD]),
         "iemic_get_suno": (C.c_int, [vp, PD]),
+        "iemic_get_fluxes": (C.c_int, [vp, PD, PD, PD]),
+        "iemic_set_emip": (C.c_int, [vp, C.c_char, PD]),
+        "iemic_get_emip": (C.c_int, [vp, C.c_char, PD]),
+        "iemic_set_tatm": (C.c_int, [vp, PD]),
         "iemic_atmos_default_params": (C.c_int, [P(AtmosParams)]),
         "iemic_atmos_create": (C.c_int, [P(vp), vp, P(AtmosParams)]),
         "iemic_atmos_destroy": (None, [vp]),
@@ -239,6 +243,7 @@ EXPORTED = ("iemic_abi_version", "iemic_create", "iemic_create_dist", "iemic_com
             "iemic_ilu_create", "iemic_ilu_compute", "iemic_ilu_apply", "iemic_ilu_apply_dev",
             "iemic_ilu_stats", "iemic_ilu_destroy",
             "iemic_set_atmosphere", "iemic_get_deps", "iemic_get_suno",
+            "iemic_get_fluxes", "iemic_set_emip", "iemic_get_emip", "iemic_set_tatm",
             "iemic_atmos_default_params", "iemic_atmos_create", "iemic_atmos_destroy",
             "iemic_atmos_dim", "iemic_atmos_set_par", "iemic_atmos_set_state",
             "iemic_atmos_get_state", "iemic_atmos_set_sst", "iemic_atmos_rhs",

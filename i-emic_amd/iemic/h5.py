@@ -275,11 +275,12 @@ class _Writer:
         return self.alloc(hdr + body)
 
     def dataset(self, arr: np.ndarray, attrs: Optional[dict] = None) -> int:
-        arr = np.ascontiguousarray(arr)
+        shape = np.shape(arr)             # a 0-d array stays a scalar dataspace, as the
+        arr = np.ascontiguousarray(arr)   # reference writes its scalars (ascontiguousarray gives 1-d)
         if arr.dtype.byteorder == ">":
             arr = arr.astype(arr.dtype.newbyteorder("<"))
         addr = self.alloc(arr.tobytes())
-        msgs = [(0x01, _dspace_msg(arr.shape)), (0x03, _dtype_msg(arr.dtype)),
+        msgs = [(0x01, _dspace_msg(shape)), (0x03, _dtype_msg(arr.dtype)),
                 (0x05, bytes([2, 2, 2, 0])),          # fill value v2: never written, undefined
                 (0x08, bytes([3, 1]) + struct.pack("<QQ", addr, arr.nbytes))]
         for name, val in (attrs or {}).items():

@@ -287,13 +287,78 @@ class Ocean:
         check(lib().iemic_get_intcond_correction(self._h, C.byref(v)), "iemic_get_intcond_correction")
         return v.value
 
+    # ---- surface fluxes and inserted forcing fields ------------------------------------
+    FLUX_GROUPS = ("SalinityFlux", "OceanAtmosSalFlux", "OceanSeaIceSalFlux", "TemperatureFlux",
+                   "ShortwaveFlux", "SensibleHeatFlux", "LatentHeatFlux", "SeaIceHeatFlux")
+
+    def _surface_gather(self, a: np.ndarray) -> np.ndarray:
+        """whole surface fields from the owned parts (zero elsewhere) of every rank"""
+        if self.layout()["nranks"] > 1:
+            check(lib().iemic_allreduce_sum(self._h, ptr(a), a.size), "iemic_allreduce_sum")
+        return a
+
+    def getFluxes(self) -> dict:
+        """THCM::getFluxes (THCM.C:1559-1593) of the current state: the eight n*m fields
+        Ocean::additionalExports writes, keyed by their group names, "SeaIceMask" and the
+        salinity correction times COMB*SALT ("Correction", THCM::scorr_).  Index (j, i)
+        with i fastest.  No sea-ice model: its fields are zero.  With a coupled atmosphere the
+        heat fluxes are dimensional, as in the reference.  Collective over the ranks; every
+        rank gets the whole fields."""
+        nm = self.cfg.n * self.cfg.m
+        out = np.zeros(9 * nm)
+        sc = C.c_double()
+        check(lib().iemic_get_fluxes(self._h, None, ptr(out), C.byref(sc)), "iemic_get_fluxes")
+        out = self._surface_gather(out).reshape(9, nm)
+        d = {name: out[q].copy() for q, name in enumerate(self.FLUX_GROUPS)}
+        d["SeaIceMask"] = out[8].copy()
+        d["Correction"] = sc.value
+        return d
+
+    def setEmip(self, field, mode: str = "E") -> None:
+        """THCM::setEmip (THCM.C:1486-1514): the whole n*m surface field replaces emip
+        (mode 'E'), adapted_emip ('A') or spert ('P') in the forcing, masked with the top
+        layer of the land mask; None restores the idealized profile."""
+        fp = None
+        if field is not None:
+            field = np.ascontiguousarray(field, dtype=np.float64).reshape(-1)
+            if field.size != self.cfg.n * self.cfg.m:
+                raise IemicError(f"setEmip: field of {field.size} values, the surface has "
+                                 f"{self.cfg.n * self.cfg.m}")
+            fp = ptr(field)
+        check(lib().iemic_set_emip(self._h, mode.encode(), fp), "iemic_set_emip")
+
+    def getEmip(self, mode: str = "E") -> np.ndarray:
+        """THCM::getEmip (THCM.C:1530-1556): the field the forcing uses; 'E' times 1 - landm."""
+        out = np.zeros(self.cfg.n * self.cfg.m)
+        check(lib().iemic_get_emip(self._h, mode.encode(), ptr(out)), "iemic_get_emip")
+        return out
+
+    def setTatm(self, field) -> None:
+        """THCM::setTatm (THCM.C:1466-1483): tatm of the ocean-only temperature forcing (a
+        heat flux with TRES = 0); None restores the idealized profile."""
+        fp = None
+        if field is not None:
+            field = np.ascontiguousarray(field, dtype=np.float64).reshape(-1)
+            if field.size != self.cfg.n * self.cfg.m:
+                raise IemicError(f"setTatm: field of {field.size} values, the surface has "
+                                 f"{self.cfg.n * self.cfg.m}")
+            fp = ptr(field)
+        check(lib().iemic_set_tatm(self._h, fp), "iemic_set_tatm")
+
     # ---- state files (Model::saveStateToFile / loadStateFromFile, Model.H:149-330) -----
-    def saveStateToFile(self, filename: str) -> None:
+    def saveStateToFile(self, filename: str, save_salinity_flux: bool = True,
+                        save_temperature_flux: bool = True, save_mask: bool = True) -> None:
         """HDF5 file in the reference's layout (EpetraExt::HDF5 conventions): State
         (an Epetra_MultiVector: Values, GlobalLength, NumVectors, __type__), Parameters (one
         scalar per continuation parameter, THCM::int2par names), Grid (n, m, l, nun, aux,
-        bounds in radians, hdim, the uniform horizontal coordinates) and Ocean's MaskGlobal
-        (Ocean.C:1904-2113).  Written by iemic.h5 (no libhdf5 in this build)."""
+        bounds in radians, hdim, the uniform horizontal coordinates) and what
+        Ocean::additionalExports adds (Ocean.C:1904-1947): the salinity flux groups
+        (SalinityFlux, OceanAtmosSalFlux, OceanSeaIceSalFlux), the heat flux groups
+        (TemperatureFlux, ShortwaveFlux, SensibleHeatFlux, LatentHeatFlux, SeaIceHeatFlux), each
+        an Epetra_MultiVector of the n*m surface, and the masks: MaskLocal (an
+        Epetra_IntVector) and MaskGlobal (Global, GlobalSize, Surface, Label).  The keywords
+        mirror the reference's "Save salinity flux", "Save temperature flux" and "Save mask"
+        (all true by default).  Written by iemic.h5 (no libhdf5 in this build)."""
         import math
         from . import h5
         c = self.cfg
@@ -304,11 +369,15 @@ class Ocean:
         xmin, xmax = math.radians(c.xmin), math.radians(c.xmax)
         ymin, ymax = math.radians(c.ymin), math.radians(c.ymax)
         dx, dy = (xmax - xmin) / c.n, (ymax - ymin) / c.m
-        L = self.landmask().astype(np.int32)
+
+        def multivector(v):
+            return {"Values": np.asarray(v, dtype=np.float64).reshape(1, -1),
+                    "GlobalLength": np.array(v.size, dtype=np.int32),
+                    "NumVectors": np.array(1, dtype=np.int32),
+                    "__type__": np.array([b"Epetra_MultiVector"], dtype="S19")}
+
         tree = {
-            "State": {"Values": x.reshape(1, -1), "GlobalLength": np.array(len(x), dtype=np.int32),
-                      "NumVectors": np.array(1, dtype=np.int32),
-                      "__type__": np.array([b"Epetra_MultiVector"], dtype="S19")},
+            "State": multivector(x),
             "Parameters": pars,
             "Grid": {"n": np.array(c.n, dtype=np.int32), "m": np.array(c.m, dtype=np.int32),
                      "l": np.array(c.l, dtype=np.int32), "nun": np.array(6, dtype=np.int32),
@@ -316,19 +385,47 @@ class Ocean:
                      "ymin": np.array(ymin), "ymax": np.array(ymax), "hdim": np.array(float(c.hdim)),
                      "x": xmin + dx * (np.arange(c.n) + 0.5), "y": ymin + dy * (np.arange(c.m) + 0.5),
                      "xu": xmin + dx * np.arange(1, c.n + 1), "yv": ymin + dy * np.arange(1, c.m + 1)},
-            "MaskGlobal": {"Global": L, "GlobalSize": np.array(L.size, dtype=np.int32),
-                           "Label": np.array([b"current"], dtype="S8")},
         }
+        if save_salinity_flux or save_temperature_flux:
+            fl = self.getFluxes()
+            groups = (self.FLUX_GROUPS[:3] if save_salinity_flux else ()) + \
+                     (self.FLUX_GROUPS[3:] if save_temperature_flux else ())
+            for name in groups:
+                tree[name] = multivector(fl[name])
+        if save_mask:
+            L = self.landmask().astype(np.int32)
+            top = L.reshape(c.l + 2, c.m + 2, c.n + 2)[c.l, 1:c.m + 1, 1:c.n + 1]
+            tree["MaskLocal"] = {"Values": L, "GlobalLength": np.array(L.size, dtype=np.int32),
+                                 "__type__": np.array([b"Epetra_IntVector"], dtype="S17")}
+            tree["MaskGlobal"] = {"Global": L, "GlobalSize": np.array(L.size, dtype=np.int32),
+                                  "Surface": np.ascontiguousarray(top).reshape(-1),
+                                  "Label": np.array([b"current"], dtype="S8")}
         h5.write(filename, tree)
 
-    def loadStateFromFile(self, filename: str) -> int:
+    def loadStateFromFile(self, filename: str, load_salinity_flux: bool = False,
+                          load_temperature_flux: bool = False) -> int:
         """Model::loadStateFromFile: the state (global length must match), every parameter
         the file holds under a THCM name (unknown names are skipped, as the reference's
-        try/catch does; the older label FPER is read as Flux Perturbation), and for an
-        SRES = 0 grid the integral-condition correction of the loaded state (Ocean.C:144-148).
+        try/catch does; the older label FPER is read as Flux Perturbation), Ocean's
+        additionalImports (Ocean.C:1950-2057) and for an SRES = 0 grid the
+        integral-condition correction of the loaded state (Ocean.C:144-148).
+
+        load_salinity_flux ("Load salinity flux"): SalinityFlux becomes emip (setEmip),
+        AdaptedSalinityFlux, if present, adapted_emip (mode 'A') and AdaptedSalinityFlux_Mask
+        spert (mode 'P').  load_temperature_flux ("Load temperature flux"): TemperatureFlux
+        becomes tatm (setTatm).  As in the reference (Ocean.C:110-120, 1958-1962) a salinity
+        flux cannot be loaded with restoring or coupled salinity, a temperature flux not with
+        restoring or coupled temperature, and a missing group is an error.
         Returns 1 (state untouched) if the file does not exist, 0 otherwise."""
         import os
         from . import h5
+        c = self.cfg
+        if load_salinity_flux and (c.sres == 1 or c.coupled_s == 1):
+            raise IemicError("Invalid configuration: a salinity flux cannot be loaded with "
+                             "restoring (SRES = 1) or coupled salinity")
+        if load_temperature_flux and (c.tres == 1 or c.coupled_t == 1):
+            raise IemicError("Invalid configuration: a temperature flux cannot be loaded with "
+                             "restoring (TRES = 1) or coupled temperature")
         if not os.path.exists(filename):
             return 1
         t = h5.read(filename)
@@ -337,6 +434,9 @@ class Ocean:
         x = np.asarray(t["/State/Values"][0], dtype=np.float64).reshape(-1)
         if x.size != self.N:
             raise IemicError(f"{filename}: state of length {x.size}, this model has {self.N}")
+        for flag, group in ((load_salinity_flux, "SalinityFlux"), (load_temperature_flux, "TemperatureFlux")):
+            if flag and f"/{group}/Values" not in t:
+                raise IemicError(f"The group <{group}> is not contained in hdf5 {filename}")
         self.setState(x)
         alias = {"FPER": "Flux Perturbation"}
         for path, (v, _) in t.items():
@@ -345,6 +445,18 @@ class Ocean:
             name = alias.get(path.split("/", 2)[2], path.split("/", 2)[2])
             if name in PAR_INDEX:
                 self.setPar(name, float(np.asarray(v).reshape(-1)[0]))
+
+        def surface(group):
+            return np.asarray(t[f"/{group}/Values"][0], dtype=np.float64).reshape(-1)
+
+        if load_salinity_flux:
+            self.setEmip(surface("SalinityFlux"), "E")
+            if "/AdaptedSalinityFlux/Values" in t:
+                self.setEmip(surface("AdaptedSalinityFlux"), "A")
+            if "/AdaptedSalinityFlux_Mask/Values" in t:
+                self.setEmip(surface("AdaptedSalinityFlux_Mask"), "P")
+        if load_temperature_flux:
+            self.setTatm(surface("TemperatureFlux"))
         if self.rowintcon >= 0:
             self.setIntCondCorrection()
         return 0

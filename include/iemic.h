@@ -45,9 +45,9 @@ extern "C" {
 
 /* Version of this header's structs and entry points.  Bumped whenever a struct changes
  * size or meaning (5: iemic_solve_info gained `safeguard` in round 4, the device vector
- * algebra of round 5); a caller built against another header must refuse to run:
+ * algebra of round 5; 7: surface fluxes and inserted forcing fields); a caller built against another header must refuse to run:
  *   if (iemic_abi_version() != IEMIC_ABI_VERSION) abort(); */
-#define IEMIC_ABI_VERSION 6
+#define IEMIC_ABI_VERSION 7
 int iemic_abi_version(void);
 
 typedef struct iemic_ctx iemic_ctx;
@@ -190,6 +190,27 @@ int iemic_psim(iemic_ctx* ctx, double* psim_min, double* psim_max, double* psim)
 /* Ocean::integralChecks (Ocean.C:1841-1848, THCM.C:2042-2118, integrals.F90:17-89): volume
  * integrals of the salt advection / diffusion operators of the state */
 int iemic_integral_checks(iemic_ctx* ctx, double* salt_advection, double* salt_diffusion);
+
+/* ---- surface fluxes and inserted forcing fields ------------------------------------ */
+/* THCM::getFluxes (THCM.C:1559-1593; get_salflux / get_temflux, probe.F90:200-355), the
+ * fields Ocean::additionalExports writes (Ocean.C:1904-1929).  x: global state in reference
+ * order, or NULL for the current state.  out: [9][n*m], field-major in the order of THCM's
+ * enum -- SalinityFlux, OceanAtmosSalFlux, OceanSeaIceSalFlux, TemperatureFlux,
+ * ShortwaveFlux, SensibleHeatFlux, LatentHeatFlux, SeaIceHeatFlux, sea-ice mask -- each
+ * (j, i) with i fastest; a rank writes the surface cells it owns.  There is no sea-ice
+ * model: the sea-ice fields are zero.  scorr: the qint correction of the salinity flux
+ * times COMB*SALT (THCM::scorr_), identical on every rank.  Collective. */
+int  iemic_get_fluxes(iemic_ctx* ctx, const double* x, double* out, double* scorr);
+/* THCM::setEmip / getEmip (THCM.C:1486-1514, 1530-1556; inserts.F90:164-224,
+ * probe.F90:140-197): mode 'E' emip, 'A' adapted_emip, 'P' spert; whole n*m surface
+ * fields on every rank.  A set field (masked with 1 - landm of the top layer) replaces the
+ * idealized profile in the forcing until it is set to NULL; 'E' is returned times
+ * 1 - landm. */
+int  iemic_set_emip(iemic_ctx* ctx, char mode, const double* field_nm);
+int  iemic_get_emip(iemic_ctx* ctx, char mode, double* out_nm);
+/* THCM::setTatm (THCM.C:1466-1483, inserts.F90:227-245): tatm of the ocean-only
+ * temperature forcing (a heat flux with TRES = 0); NULL restores the profile */
+int  iemic_set_tatm(iemic_ctx* ctx, const double* field_nm);
 
 /* ---- parameters (setparcs_/getparcs_, usrc.F90:163-198; index 1..30 = par2int) --- */
 int  iemic_set_par(iemic_ctx* ctx, int idx, double value);
