@@ -247,15 +247,15 @@ int assemble_jacobian(iemic_ctx* c, const double* x_dev)
     if (rc) return rc;
     BlockGS& gs = c->gs;
     if (gs.ready && gs.kind == 2) {
-        /* the block GS reads its set-up Jacobian (BlockGS::vp): assemble into the other buffer */
-        if (gs.vp == c->d_val.p) {
-            if (gs.vold.n != c->d_val.n && gs.vold.alloc(c->d_val.n)) {
+        /* the block GS reads its set-up Jacobian (ActiveSet::vp): assemble into the other buffer */
+        if (gs.act.vp == c->d_val.p) {
+            if (gs.act.vold.n != c->d_val.n && gs.act.vold.alloc(c->d_val.n)) {
                 set_error("assemble_jacobian: out of device memory for the second Jacobian buffer");
                 return IEMIC_ENOMEM;
             }
-            std::swap(c->d_val, gs.vold);
+            std::swap(c->d_val, gs.act.vold);
         }
-        gs.coef_stale = 1;
+        gs.act.coef_stale = 1;
     }
     Geo g = c->geo();
     dim3 blk(128), grd((unsigned)((c->nloc + 127) / 128), NUN);

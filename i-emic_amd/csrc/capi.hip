@@ -540,7 +540,7 @@ extern "C" int iemic_layout(const iemic_ctx* c, int64_t* out)
 extern "C" int iemic_active_cells(const iemic_ctx* c, int64_t* nact)
 {
     if (!c || !nact) return IEMIC_EINVAL;
-    *nact = c->gs.ready && c->gs.kind == 2 ? c->gs.nact : 0;
+    *nact = c->gs.ready && c->gs.kind == 2 ? c->gs.act.nact : 0;
     return 0;
 }
 

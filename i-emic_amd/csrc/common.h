@@ -33,6 +33,8 @@ void set_error(const std::string& s);
 template <typename T> struct DevBuf {
     T* p = nullptr;
     size_t n = 0;
+    /* grow-only: at least count elements (the contents are lost when it grows) */
+    int reserve(size_t count) { return n < count ? alloc(count) : 0; }
     int alloc(size_t count)
     {
         free();
@@ -155,17 +157,116 @@ int cr_check(iemic_ctx* c, SchurCR& cr);
 int cr_solve(iemic_ctx* c, const SchurCR& cr, const double* b, double* x, hipStream_t s, double* xT = nullptr);
 int cr_inverse_dev(hipStream_t s, int m, const double* src, double* dst, int* info);
 
+/* T/S aggregation multigrid of the block GS (ts_mg.hip; BlockGS::mg, which no other unit
+ * names): 2x2 horizontal aggregates, full depth, band-local; level q has n[q] x m[q] x l cells
+ * in the k-contiguous level layout (ts_mg.hip TsLev; level 0 packed from tsoff/tsdiag) with
+ * 16 couplings, the 2x2 block, the z-line factors (12), rhs and iterate */
+struct TsMg {
+    static constexpr int MAX = 12;
+    int sweeps = 1, nlev = 0;
+    int n[MAX] = {}, m[MAX] = {};
+    int par[MAX] = {};               /* colour parity of the level's cell (0, 0): global   */
+                                     /* column + row offset of the subdomain's aggregates  */
+    DevBuf<double> off[MAX], diag[MAX], fac[MAX], b[MAX], z[MAX];
+    DevBuf<double> zu[MAX];          /* fused up leg (k_mg_up): the post-smoothed iterate      */
+    DevBuf<double> cinv;             /* coarsest level: dense inverse (2 ncl)^2          */
+    /* subdomains: the coarsest T/S level solved globally (all ranks' coarsest cells plus
+     * the cross-subdomain couplings; band LU + inverse on the device, on every rank) */
+    int glob = 0, gN = 0, gGX = 0, gI0 = 0, gJ0 = 0;
+    DevBuf<double> gX, gband, gvec, gtmp, glpan;
+    DevBuf<int> gpiv, ginfo, gcols;
+    DevBuf<double> cdense;           /* coarsest dense operator (device assembly)        */
+    /* one rank: the coarsest level is the first of <= CR_CELLS cells whose columns of
+     * one longitude fit a cyclic-reduction block (2 mb l <= 192); its inverse (cinv, in
+     * the level's unknown order) comes from a whole-problem cyclic reduction over
+     * longitudes (schur_cr.hip, the explicit "tail" inverse) */
+    static constexpr int CR_CELLS = 1024;
+    int crd = 0;
+    int hr = 0;                      /* bands: level 0 has 2 halo rows, and its colour-1   */
+                                     /* lines on them are relaxed here too (mg_vcycle)      */
+    SchurCR cr;
+    DevBuf<int> cinfo;               /* its Gauss-Jordan pivot flag                      */
+};
+/* stores sweeps; with BlockGS::ts_mg > 0: levels, Galerkin operators, z-line factors and the
+ * coarsest inverse (once per Jacobian), ts_mg = 0 where the grid has no coarse level */
+int ts_mg_setup(iemic_ctx* c, int sweeps);
+/* BlockGS::ts_mg V-cycles on rr_TS - A_TS,D zd; z(T, S) is written when out, else by
+ * ts_mg_out.  side: the V-cycles on iemic_ctx::side, ev_join recorded after them */
+int ts_mg_solve(iemic_ctx* c, const double* zd, double* z, bool out, bool side);
+int ts_mg_out(iemic_ctx* c, double* z);
+
+/* band_lu.hip: band LU with partial pivoting and the explicit inverse, panels of BAND_NBP
+ * columns (lpan: ceil(N / BAND_NBP) x (BAND_NBP + bl) x BAND_NBP multipliers) */
+constexpr int BAND_NBP = 16;
+int band_lu_inverse(iemic_ctx* c, double* ab, int N, int bl, int bu, int* piv, int* info_d, double* lpan,
+                    const int* cols, double* X, int* info);
+
+/* The compressed active-cell set and the coefficient streams packed from the Jacobian
+ * (active_set.hip; BlockGS::act).  This is the part of the block GS that krylov.hip and
+ * assembly.hip may read; beside it they read only BlockGS::ready, kind, known, rrP, dyn_iters
+ * and dyn_mr. */
+struct ActiveSet {
+    /* owned cells with a non-identity row (the rest: land, all six rows identity), ascending:
+     * FGMRES keeps its Arnoldi basis on these cells only (krylov.hip) */
+    DevBuf<int> act;
+    DevBuf<int> cmap;                /* per owned cell: its index in act, -1 (land)        */
+    int64_t ric = -1;                /* compressed row of the integral condition (owned)   */
+    DevBuf<uint8_t> actf;            /* per owned cell: 1 active (k_cell_active)           */
+    int64_t nact = 0;
+    std::vector<uint8_t> act_h;      /* the per-cell flags the list was built from        */
+    /* the compressed SpMV (krylov.hip k_spmv7c): the active cells' 104 coefficients blocked
+     * per tile (k_spmv_pack: no coefficient line holds a land cell or another tile's), and
+     * the grid tiles that hold an active cell (8 ints each: tile, first | last active lane
+     * << 8, first active cell, active cells, 64-bit active-lane mask, 0, 0) */
+    DevBuf<double> spc;
+    DevBuf<int> atl;
+    DevBuf<int> apos;                /* per active cell: its tile's index in atl            */
+    int natile = 0;
+    DevBuf<double> dvh;              /* bands: U/V/W/P coefficients of the two halo rows  */
+    DevBuf<double> dvb;              /* the active cells' U/V/W/P coefficients, blocked:  */
+                                     /* [act / 64][slot][act % 64] (the defect's stream)  */
+    /* the Jacobian the apply reads: the set-up one (gs_refresh).  A Jacobian assembled
+     * while the block GS is set up goes into the other buffer (assemble_jacobian swaps
+     * iemic_ctx::d_val with vold), so the preconditioner stays the operator of its set-up
+     * Jacobian on every rank, as the reference's extracted blocks do */
+    const double* vp = nullptr;
+    DevBuf<double> vold;
+    /* a Jacobian was assembled since the set-up: the compressed SpMV's stream spc and the
+     * identity-row check are redone before the next apply or solve (gs_refresh) */
+    int coef_stale = 0;
+    int cmp_ok = 0;                  /* the active list matches the Jacobian's identity rows */
+    DevBuf<double> chk;              /* gs_refresh: identity-row mismatches (1 double)     */
+};
+/* the list, cmap, ric and the tiles from BlockGS::known; *changed: the list was rebuilt */
+int act_build(iemic_ctx* c, bool* changed);
+/* set-up: dvh, dvb and spc from the Jacobian just assembled, which vp keeps */
+int act_pack_streams(iemic_ctx* c);
+/* repack the coefficient copies after a new Jacobian (ActiveSet::coef_stale) */
+int gs_refresh(iemic_ctx* c);
+
+/* the plain T/S sweeps of the block GS (prec_gs.hip, ts_mg = 0); the multigrid's level 0 is
+ * packed from tsoff */
+struct TsSweeps {
+    DevBuf<double> tsinv;            /* 2x2 T/S inverses per cell                       */
+    DevBuf<double> tsoff;            /* compact T/S off-diagonal couplings, 16 x ncell  */
+    DevBuf<double> tsc, tic, bc;     /* the same per colour (even n), T/S rhs per colour */
+    DevBuf<double> zt, zs;           /* T/S iterates                                     */
+    DevBuf<double> bts;              /* T/S right-hand side (AoS)                        */
+};
+
 /* Preconditioner state (prec.hip: block Jacobi, prec_gs.hip: block Gauss-Seidel). */
 struct BlockGS {
     int ready = 0;
     int kind = 0;                    /* 1: block-Jacobi, 2: block Gauss-Seidel           */
     int ts_sweeps = 3;               /* symmetric red-black sweeps on the T/S block     */
     DevBuf<double> dinv;             /* block-Jacobi: 6x6 inverses, slot-major          */
+    TsMg mg;
+    ActiveSet act;
+    TsSweeps sw;
     /* structure (rebuilt when the identity-row pattern changes) */
     DevBuf<double> flags_d;          /* the same flags on the device (k_band_flags)       */
     std::vector<double> flags_h;     /* global (active column, U/V point) flags the      */
                                      /* structure was built for                         */
-    int ncol = 0;                    /* active water columns                            */
     DevBuf<int> own_pos;             /* Schur index -> itself for this band's active     */
                                      /* columns, -1 otherwise                           */
     DevBuf<int> ocol;                /* (j*n+i) -> this band's Schur rhs entry, -2 - entry */
@@ -179,53 +280,21 @@ struct BlockGS {
     DevBuf<int> ij_of_col;           /* Schur index -> j*n+i                            */
     DevBuf<uint8_t> pinned;          /* Schur index pinned to 0 (null-space pins)       */
     /* numeric factors */
-    DevBuf<double> uvinv, tsinv;     /* 2x2 inverses per cell (U/V and T/S blocks)      */
+    DevBuf<double> uvinv;            /* 2x2 U/V inverses per cell                       */
+    DevBuf<double> tsdiag;           /* fine 2x2 T/S blocks (active entries; k_cell_factors, */
+                                     /* read by the multigrid's level 0)                 */
     DevBuf<double> pw;               /* per P row: weight of the depth integral         */
     DevBuf<uint64_t> kmask;          /* per cell: slots coupling to identity columns     */
-    DevBuf<double> tsoff;            /* compact T/S off-diagonal couplings, 16 x ncell  */
-    DevBuf<double> tsc, tic, bc;     /* the same per colour (even n), T/S rhs per colour */
-    DevBuf<double> zt, zs, tcell;    /* T/S iterates, per-cell work                      */
     DevBuf<double> S9;               /* Schur rows, 9 couplings per column (i*m+j)       */
     SchurCR cr;                      /* its cyclic-reduction factors                     */
     int dyn_iters = 1;               /* defect-correction passes on the dynamics block   */
     DevBuf<double> dres, zc;         /* dynamics defect and correction (ext rows)        */
-    DevBuf<double> dvh;              /* bands: U/V/W/P coefficients of the two halo rows  */
-    DevBuf<double> dvb;              /* the active cells' U/V/W/P coefficients, blocked:  */
-                                     /* [act / 64][slot][act % 64] (the defect's stream)  */
     DevBuf<double> dq, dzero, dmr;   /* MR passes: -A_DD zc, a zero vector, dot partials  */
     int dyn_mr = 0;                  /* 1: minimal-residual step length per correction   */
     double dyn_omega = 1.0;          /* fixed step of the correction passes (dyn_mr = 0) */
     int ts_at = 0;                   /* T/S rhs after this many passes (0: after all)     */
     int schur_passes = 0;            /* passes solving the Schur system: first k-1 + last (0: all) */
-    /* T/S aggregation multigrid (2x2 horizontal aggregates, full depth, band-local): level q
-     * has mg_n[q] x mg_m[q] x l cells in the k-contiguous level layout (prec_gs.hip TsLev;
-     * level 0 packed from tsoff/tsdiag) with 16 couplings, the 2x2 block, the z-line
-     * factors (12), rhs and iterate */
-    static constexpr int MG_MAX = 12;
-    int ts_mg = 1, mg_sweeps = 1, mg_nlev = 0;
-    int mg_n[MG_MAX] = {}, mg_m[MG_MAX] = {};
-    int mg_par[MG_MAX] = {};         /* colour parity of the level's cell (0, 0): global   */
-                                     /* column + row offset of the subdomain's aggregates  */
-    DevBuf<double> tsdiag;           /* fine 2x2 T/S blocks (active entries)              */
-    DevBuf<double> mg_off[MG_MAX], mg_diag[MG_MAX], mg_fac[MG_MAX], mg_b[MG_MAX], mg_z[MG_MAX];
-    DevBuf<double> mg_zu[MG_MAX];    /* fused up leg (k_mg_up): the post-smoothed iterate      */
-    DevBuf<double> mg_cinv;          /* coarsest level: dense inverse (2 ncl)^2          */
-    /* subdomains: the coarsest T/S level solved globally (all ranks' coarsest cells plus
-     * the cross-subdomain couplings; band LU + inverse on the device, on every rank) */
-    int mg_glob = 0, mg_gN = 0, mg_gGX = 0, mg_gI0 = 0, mg_gJ0 = 0;
-    DevBuf<double> mg_gX, mg_gband, mg_gvec, mg_gtmp, mg_glpan;
-    DevBuf<int> mg_gpiv, mg_ginfo, mg_gcols;
-    DevBuf<double> mg_cdense;        /* coarsest dense operator (device assembly)        */
-    /* one rank: the coarsest level is the first of <= MG_CR_CELLS cells whose columns of
-     * one longitude fit a cyclic-reduction block (2 mb l <= 192); its inverse (mg_cinv, in
-     * the level's unknown order) comes from a whole-problem cyclic reduction over
-     * longitudes (schur_cr.hip, the explicit "tail" inverse) */
-    static constexpr int MG_CR_CELLS = 1024;
-    int mg_crd = 0;
-    int mg_hr = 0;                   /* bands: level 0 has 2 halo rows, and its colour-1   */
-                                     /* lines on them are relaxed here too (mg_vcycle)      */
-    SchurCR mg_cr;
-    DevBuf<int> mg_cinfo;            /* its Gauss-Jordan pivot flag                      */
+    int ts_mg = 1;                   /* T/S multigrid V-cycles per apply (0: the sweeps)  */
     /* the dynamics passes work on component-planar copies (plane q = unknown q of every ext
      * cell, plane stride next): known flags, iterate and right-hand side; dres, zc, dq and
      * dzero are planar too.  The AoS rr is kept for the T/S sweeps (ts_mg = 0) */
@@ -233,35 +302,8 @@ struct BlockGS {
     DevBuf<double> zP, rrP;
     DevBuf<double> colvT;            /* the Schur solution transposed (j * n + i)          */
     DevBuf<double> colvZ;            /* zeros of colvT's size: pbar of a pass without Schur  */
-    DevBuf<double> rr, bts, colv, colv2, colv_own; /* work: Schur rhs (colv_own; bands:  */
+    DevBuf<double> rr, colv, colv2, colv_own; /* work: Schur rhs (colv_own; bands:       */
                                      /* summed into colv), solution colv2               */
-    /* owned cells with a non-identity row (the rest: land, all six rows identity), ascending:
-     * FGMRES keeps its Arnoldi basis on these cells only (krylov.hip) */
-    DevBuf<int> act;
-    DevBuf<int> cmap;                /* per owned cell: its index in act, -1 (land)        */
-    int64_t ric = -1;                /* compressed row of the integral condition (owned)   */
-    DevBuf<uint8_t> actf;            /* per owned cell: 1 active (k_cell_active)           */
-    int64_t nact = 0;
-    std::vector<uint8_t> act_h;      /* the per-cell flags the list was built from        */
-    /* the compressed SpMV (krylov.hip k_spmv7c): the active cells' 104 coefficients blocked
-     * per tile (prec_gs.hip k_spmv_pack: no coefficient line holds a land cell or another
-     * tile's), and the grid tiles that hold an active cell (8 ints each: tile, first | last
-     * active lane << 8, first active cell, active cells, 64-bit active-lane mask, 0, 0) */
-    DevBuf<double> spc;
-    DevBuf<int> atl;
-    DevBuf<int> apos;                /* per active cell: its tile's index in atl            */
-    int natile = 0;
-    /* the Jacobian the apply reads: the set-up one (prec_gs.hip gs_refresh).  A Jacobian
-     * assembled while the block GS is set up goes into the other buffer (assemble_jacobian
-     * swaps iemic_ctx::d_val with vold), so the preconditioner stays the operator of its
-     * set-up Jacobian on every rank, as the reference's extracted blocks do */
-    const double* vp = nullptr;
-    DevBuf<double> vold;
-    /* a Jacobian was assembled since the set-up: the compressed SpMV's stream spc and the
-     * identity-row check are redone before the next apply or solve (gs_refresh) */
-    int coef_stale = 0;
-    int cmp_ok = 0;                  /* the active list matches the Jacobian's identity rows */
-    DevBuf<double> chk;              /* gs_refresh: identity-row mismatches (1 double)     */
 };
 
 struct Krylov {
@@ -269,7 +311,7 @@ struct Krylov {
     DevBuf<double> V, Z;             /* (m+1) x N and m x N                             */
     DevBuf<double> w, r;
     /* DCGS2 with the block GS: the Arnoldi basis compressed to the active cells
-     * (BlockGS::act, 6 nact rows per vector), the preconditioner input rf (full, zero on
+     * (ActiveSet::act, 6 nact rows per vector), the preconditioner input rf (full, zero on
      * the land cells) and, for a right-hand side with land-cell entries, t and b' */
     int mc = 0;
     int64_t nc = 0;
@@ -485,11 +527,9 @@ int fgmres(iemic_ctx* c, const double* b, double* x, const iemic_krylov* opt,
 /* prec.hip */
 int prec_compute(iemic_ctx* c, const iemic_krylov* opt);
 int prec_apply(iemic_ctx* c, const double* r, double* z);
-/* the block GS apply from a compressed input (6 rows per BlockGS::act cell, zero land rows) */
+/* the block GS apply from a compressed input (6 rows per ActiveSet::act cell, zero land rows) */
 /* staged: rc is already in the block GS's planar right-hand side (k_dcgs_update) */
 int gs_apply_c(iemic_ctx* c, const double* rc, double* z, bool staged = false);
-/* repack the block GS's coefficient copies after a new Jacobian (BlockGS::coef_stale) */
-int gs_refresh(iemic_ctx* c);
 /* y = J x written compressed (rows of the active cells only; x full, halo current) */
 int spmv_kernel_c(iemic_ctx* c, const double* x, double* yc, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 }  // namespace iemic

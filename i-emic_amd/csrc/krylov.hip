@@ -153,14 +153,14 @@ __global__ void __launch_bounds__(256) k_spmv7(SubLay X, const double* __restric
  * slot-major Jacobian, whose 128-byte coefficient lines hold 16 cells: the lines of mixed land /
  * water runs are fetched whole (at 2 degrees 128.9 MB of coefficient lines for 100.7 MB of
  * active coefficients; round 5's land-skipping variant moved 147 MB per launch, 1.25x).
- *  - Coefficients: BlockGS::spc holds the active cells' 104 slots blocked per tile -- the na
+ *  - Coefficients: ActiveSet::spc holds the active cells' 104 slots blocked per tile -- the na
  *    active cells of a tile (consecutive in the compressed order, from a0) as one contiguous
  *    run of 104 na doubles, slot s of the tile's r-th active cell at 104 a0 + s na + r -- so a
  *    workgroup streams one run that no land cell and no other tile shares (PMC: 117.1 MB per
  *    launch against 117.7 MB algorithmic; slot-major packing over the active list: 124.9 MB,
  *    3.4 us slower).
  *  - Tiles: only the 64-cell tiles (one grid row) that hold an active cell are launched
- *    (BlockGS::atl: tile, first / last active lane, a0, na and the 64-bit active-lane mask, so
+ *    (ActiveSet::atl: tile, first / last active lane, a0, na and the 64-bit active-lane mask, so
  *    a lane finds its compressed index by a popcount instead of a dependent load), dealt to
  *    the 8 XCDs in contiguous runs.
  *  - x: the six (dj, dk) neighbour rows' interior cells are contiguous runs in x and in the
@@ -304,10 +304,10 @@ __device__ __forceinline__ void dyn_partial(const double* __restrict__ val, cons
     }
 }
 /* hv (latitude bands): tiles past the owned ones compute the defect on the two halo rows
- * too (their coefficients exchanged once per Jacobian, BlockGS::dvh; z with a 2-deep halo),
+ * too (their coefficients exchanged once per Jacobian, ActiveSet::dvh; z with a 2-deep halo),
  * so that the next dynamics pass needs no exchange of d.  hs / hn: the south / north halo row
  * exists (a neighbour band).  alist: the owned tiles run over the active cells only (the
- * compressed basis' list, BlockGS::act; about half the cells are land at 2 degrees): d of the
+ * compressed basis' list, ActiveSet::act; about half the cells are land at 2 degrees): d of the
  * other cells stays 0 (gs_compute zeroes it whenever the list changes). */
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 8))) k_spmv_dyn(SubLay X, const double* __restrict__ val,
                                                   const double* __restrict__ z,
@@ -383,17 +383,17 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 8))
 int spmv_dyn_defect(iemic_ctx* c, const double* z, const double* r, const uint8_t* knP, double* d, bool halo)
 {
     const BlockGS& gs = c->gs;
-    const bool al = gs.act.p && gs.nact > 0;
-    const int64_t nown = al ? gs.nact : c->nloc;
+    const bool al = gs.act.act.p && gs.act.nact > 0;
+    const int64_t nown = al ? gs.act.nact : c->nloc;
     const int nblk = (int)((nown + 63) / 64);
     const int64_t row = (int64_t)c->l * c->nx;
-    const bool hv = halo && gs.dvh.p;
+    const bool hv = halo && gs.act.dvh.p;
     const int nhb = hv ? (int)((2 * row + 63) / 64) : 0;
     const unsigned grid = 8u * (unsigned)((nblk + nhb + 7) / 8);
-    hipLaunchKernelGGL(k_spmv_dyn, dim3(grid), dim3(256), 0, c->stream, sub_lay(c), gs.vp, z, r, knP, d,
-                       c->nloc, nblk, (int64_t)c->next, hv ? gs.dvh.p : nullptr, nhb,
-                       hv && c->nb[2] >= 0 ? 1 : 0, hv && c->nb[3] >= 0 ? 1 : 0, al ? gs.act.p : nullptr, nown,
-                       al && gs.dvb.p ? gs.dvb.p : nullptr);
+    hipLaunchKernelGGL(k_spmv_dyn, dim3(grid), dim3(256), 0, c->stream, sub_lay(c), gs.act.vp, z, r, knP, d,
+                       c->nloc, nblk, (int64_t)c->next, hv ? gs.act.dvh.p : nullptr, nhb,
+                       hv && c->nb[2] >= 0 ? 1 : 0, hv && c->nb[3] >= 0 ? 1 : 0, al ? gs.act.act.p : nullptr, nown,
+                       al && gs.act.dvb.p ? gs.act.dvb.p : nullptr);
     return 0;
 }
 
@@ -448,21 +448,6 @@ __global__ void k_mdot_final(const double* __restrict__ partial, int nb, int nve
     for (int b = threadIdx.x; b < nb; b += blockDim.x) s += partial[(int64_t)i * nb + b];
     double t = block_sum(s, sm);
     if (threadIdx.x == 0) out[i] = t;
-}
-/* w -= sum_i h_i V_i */
-__global__ void __launch_bounds__(256) k_mupdate(const double* __restrict__ V, int64_t ldv, int nvec,
-                                                 const double* __restrict__ h,
-                                                 double* __restrict__ w, int64_t N)
-{
-    __shared__ double hs[1024];
-    for (int i = threadIdx.x; i < nvec; i += blockDim.x) hs[i] = h[i];
-    __syncthreads();
-    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < N;
-         q += (int64_t)gridDim.x * blockDim.x) {
-        double acc = w[q];
-        for (int i = 0; i < nvec; i++) acc -= hs[i] * V[(int64_t)i * ldv + q];
-        w[q] = acc;
-    }
 }
 /* w -= sum_i h_i V_i and partial[blk] = block's sum of the new w^2 (grid = RED_BLOCKS) */
 __global__ void __launch_bounds__(256) k_mupdate_norm(const double* __restrict__ V, int64_t ldv,
@@ -868,23 +853,23 @@ static int spmv_intcond(iemic_ctx* c, const double* x, double* yr)
 int spmv_kernel_c(iemic_ctx* c, const double* x, double* yc, hipEvent_t ev0, hipEvent_t ev1)
 {
     const BlockGS& gs = c->gs;
-    if (!c->jac_valid || !gs.cmap.p || !gs.spc.p || !gs.atl.p || gs.coef_stale) {
+    if (!c->jac_valid || !gs.act.cmap.p || !gs.act.spc.p || !gs.act.atl.p || gs.act.coef_stale) {
         set_error("spmv: no Jacobian, no active-cell map or stale packed coefficients");
         return IEMIC_ESTATE;
     }
     hipStream_t s = c->stream;
     const int tpr = (c->nx + SP7_T - 1) / SP7_T;
-    const unsigned grid = 8u * (unsigned)((gs.natile + 7) / 8);
-    if (gs.natile > 0)
-        hipExtLaunchKernelGGL(k_spmv7c, dim3(grid), dim3(256), 0, s, ev0, ev1, 0, sub_lay(c), (const double*)gs.spc.p,
-                              x, yc, (const int4*)gs.atl.p, gs.natile, tpr);
+    const unsigned grid = 8u * (unsigned)((gs.act.natile + 7) / 8);
+    if (gs.act.natile > 0)
+        hipExtLaunchKernelGGL(k_spmv7c, dim3(grid), dim3(256), 0, s, ev0, ev1, 0, sub_lay(c), (const double*)gs.act.spc.p,
+                              x, yc, (const int4*)gs.act.atl.p, gs.act.natile, tpr);
     double* yr = nullptr;
     if (c->rowintcon >= 0) {
-        if (c->gs.ric < 0) {
+        if (c->gs.act.ric < 0) {
             set_error("spmv: the integral-condition row lies in an inactive cell");
             return IEMIC_EINVAL;
         }
-        yr = yc + c->gs.ric;
+        yr = yc + c->gs.act.ric;
     }
     return spmv_intcond(c, x, yr);
 }
@@ -1072,9 +1057,9 @@ int fgmres(iemic_ctx* c, const double* b, double* x, const iemic_krylov* opt, ie
     const BlockGS& gs = c->gs;
     int rc = opt->prec > 0 ? gs_refresh(c) : 0;
     if (rc) return rc;
-    const bool cmp = opt->orth == 0 && opt->prec == 2 && gs.ready && gs.kind == 2 && gs.nact > 0 && gs.cmap.p &&
-                     gs.cmp_ok && gs.spc.p && gs.atl.p;
-    const int64_t NC = cmp ? NUN * gs.nact : 0;
+    const bool cmp = opt->orth == 0 && opt->prec == 2 && gs.ready && gs.kind == 2 && gs.act.nact > 0 && gs.act.cmap.p &&
+                     gs.act.cmp_ok && gs.act.spc.p && gs.act.atl.p;
+    const int64_t NC = cmp ? NUN * gs.act.nact : 0;
     rc = ensure_krylov(c, m, NC);
     if (rc) return rc;
     /* the staged applies (gs_apply_c after an update pass) leave the identity rows of the
@@ -1148,7 +1133,7 @@ int fgmres(iemic_ctx* c, const double* b, double* x, const iemic_krylov* opt, ie
     for (int cycle = 0; beta > 0.0 && cycle <= opt->max_restarts; cycle++) {
         const int it_c0 = it;
         if (cmp)
-            hipLaunchKernelGGL(k_cgather, dim3(GC), dim3(256), 0, c->stream, r, gs.act.p, NC, c->own0, 1.0 / beta, Vc);
+            hipLaunchKernelGGL(k_cgather, dim3(GC), dim3(256), 0, c->stream, r, gs.act.act.p, NC, c->own0, 1.0 / beta, Vc);
         else
             hipLaunchKernelGGL(k_scale_copy, dim3(G), dim3(256), 0, c->stream, r + o, 1.0 / beta, V + o, NL);
         std::fill(g.begin(), g.end(), 0.0);
@@ -1289,7 +1274,7 @@ int fgmres(iemic_ctx* c, const double* b, double* x, const iemic_krylov* opt, ie
                 HIP_OK(hipEventRecord(evr[jj & 1], c->stream));
                 if (jj < m)
                     hipLaunchKernelGGL(k_dcgs_update, dim3((unsigned)std::min<int64_t>(4096, (NQ / 2 + 255) / 256)), dim3(256), 0, c->stream, Q, LQ, nv,
-                                       c->d_hbuf.p + RED_ROWS, u, wv, NQ, cmp ? (const int*)gs.act.p : nullptr,
+                                       c->d_hbuf.p + RED_ROWS, u, wv, NQ, cmp ? (const int*)gs.act.act.p : nullptr,
                                        c->own0, (int64_t)c->next, cmp ? gs.rrP.p : nullptr);
                 return 0;
             };

@@ -1,0 +1,1681 @@
+/*
+ * ts_mg.hip -- T/S aggregation multigrid of the block Gauss-Seidel preconditioner
+ * (prec_gs.hip, step 6 with ts_mg > 0).
+ *
+ * The T/S block is an advection-diffusion operator whose smooth error modes Gauss-Seidel
+ * sweeps barely touch.  Its coarse spaces aggregate 2x2 horizontal neighbours over the
+ * full depth (each level is again an n x m x l grid with the fine coupling pattern:
+ * 6 same-variable face couplings, T<->S at k-1/k+1, a 2x2 cell block), built by Galerkin
+ * summation with piecewise-constant transfers.  Aggregates stay inside a latitude band.
+ * One V-cycle: z-line relaxation by horizontal colour on every level (colours forward
+ * before the coarse correction, backward after it), a dense inverse on the coarsest.
+ *
+ * Level layout (level 0 included, packed once per Jacobian): columns k-contiguous,
+ *     cell = ((jl + hj) * n + i) * l + k,
+ * so the P lanes of a column (lane = level k) read one contiguous run of every array and
+ * a horizontal neighbour is again one whole run (one 128-B line per array at l = 16);
+ * with hj = 1 halo row on each side and hi = 1 halo column (the row width is n + 2 hi) on
+ * level 0 when the y / x direction is split over ranks (refreshed by exchanges).
+ * The z-lines are factorised at set-up (block Thomas, k_mg_fac: F = -A'^-1 B, A'^-1,
+ * Cp = A'^-1 C per cell), so a relaxation is two affine parallel scans over the lanes
+ * without a division.  Launch fusion (the apply is latency-bound):
+ *   - the T/S right-hand side and the first colour of level 0 (k_mg_entry),
+ *   - each restriction and the first colour of the coarse level (k_mg_rc): from a zero
+ *     iterate that colour's lines see zero neighbours,
+ *   - the prolongation into the first post-smoothing colour (k_mg_zl, corr): a line solve
+ *     never reads its own old value, so the coarse correction is only needed on the
+ *     neighbours not yet relaxed, and it is added where they are read,
+ *   - after one forward sweep from zero with two colours, the residual of the last colour
+ *     is zero and that of the first is -H z(last colour) (restriction shortcut: 16 instead
+ *     of 72 doubles per fine-cell pair),
+ *   - the last colour launches of the final level-0 sweep write z(T, S) straight into the
+ *     preconditioner output. */
+#include <algorithm>
+#include <cstdlib>
+#include <cmath>
+#include <vector>
+
+#include "gs_internal.h"
+
+namespace iemic {
+
+namespace {
+
+/* 3b. y = X b (X row-major nr x nc), one wavefront per row */
+__global__ void __launch_bounds__(256) k_gemv(const double* __restrict__ X, int nr, int nc,
+                                              const double* __restrict__ b, double* __restrict__ y)
+{
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= nr) return;
+    const double* xr = X + (int64_t)row * nc;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    int c = lane;
+    for (; c + 192 < nc; c += 256) {
+        s0 += xr[c] * b[c];
+        s1 += xr[c + 64] * b[c + 64];
+        s2 += xr[c + 128] * b[c + 128];
+        s3 += xr[c + 192] * b[c + 192];
+    }
+    for (; c < nc; c += 64) s0 += xr[c] * b[c];
+    double s = (s0 + s1) + (s2 + s3);
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    if (lane == 0) y[row] = s;
+}
+
+/* y = X b for a dense row-major N x N inverse (N <= 64 NL), one wave per row: every load
+ * of the row is issued before the first multiply, b staged in LDS, eight independent
+ * accumulators and a fixed shuffle tree (deterministic) */
+template <int NL>
+__global__ void __launch_bounds__(256) k_gemv_w(const double* __restrict__ X, int N, const double* __restrict__ b,
+                                                double* __restrict__ y)
+{
+    __shared__ double vb[64 * NL];
+    const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const double* A = X + (size_t)(r < N ? r : 0) * N;
+    double a[NL];
+#pragma unroll
+    for (int u = 0; u < NL; u++) {
+        const int c = lane + 64 * u;
+        a[u] = c < N ? __builtin_nontemporal_load(A + c) : 0.0;
+    }
+    for (int c = threadIdx.x; c < N; c += 256) vb[c] = b[c];
+    __syncthreads();
+    if (r >= N) return;
+    double acc[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int u = 0; u < NL; u++) {
+        const int c = lane + 64 * u;
+        if (c < N) acc[u & 7] += a[u] * vb[c];
+    }
+    double v = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    if (lane == 0) y[r] = v;
+}
+
+struct TsLev {
+    int n, mb, l, periodic;          /* periodic: the level wraps in x (one x part)        */
+    int hj, hi;                      /* halo rows / columns of the layout (level 0, split)  */
+    int vis, visi;                   /* halo rows / columns the smoother / residual read    */
+    int jpar;                        /* colour parity of (0, 0) (global i + j, level 0)     */
+    int64_t cstr;                    /* array stride (mb + 2 hj) (n + 2 hi) l              */
+    const double* off;               /* 16 x cstr: T row q 0..7, S row q 8..15            */
+    const double* diag;              /* 4 x cstr: 2x2 block (TT, TS, ST, SS)              */
+    const double* fac;               /* 12 x cstr: line factors F | A'^-1 | Cp            */
+    double* b;                       /* 2 x cstr: right-hand side (T, S)                  */
+    double* z;                       /* 2 x cstr: iterate (T, S)                          */
+};
+__host__ __device__ __forceinline__ int64_t mg_cell(const TsLev& V, int i, int jl, int k)
+{
+    return (((int64_t)jl + V.hj) * (V.n + 2 * V.hi) + i + V.hi) * V.l + k;
+}
+/* neighbour q (-i,+i,-j,+j,-k,+k) of (i,jl,k): false outside the level's (visible) band */
+__device__ __forceinline__ bool mg_nb(const TsLev& V, int q, int& i, int& jl, int& k)
+{
+    switch (q) {
+    case 0: i--; break;
+    case 1: i++; break;
+    case 2: jl--; break;
+    case 3: jl++; break;
+    case 4: k--; break;
+    default: k++; break;
+    }
+    if (jl < -V.vis || jl >= V.mb + V.vis || k < 0 || k >= V.l) return false;
+    if (i < -V.visi || i >= V.n + V.visi) {
+        if (!V.periodic) return false;
+        i = (i + V.n) % V.n;
+    }
+    return true;
+}
+/* the same neighbour, branch-free for the apply: outside the level's (visible) band the
+ * cell itself (every coupling to outside is 0: k_ts_compact / k_mg_galerkin), so the loads
+ * of all neighbours issue together */
+__device__ __forceinline__ void mg_nbc(const TsLev& V, int q, int& i, int& jl, int& k)
+{
+    switch (q) {
+    case 0: i = i > -V.visi ? i - 1 : (V.periodic ? V.n - 1 : i); break;
+    case 1: i = i < V.n - 1 + V.visi ? i + 1 : (V.periodic ? 0 : i); break;
+    case 2: jl = jl > -V.vis ? jl - 1 : jl; break;
+    case 3: jl = jl < V.mb - 1 + V.vis ? jl + 1 : jl; break;
+    case 4: k = k > 0 ? k - 1 : k; break;
+    default: k = k < V.l - 1 ? k + 1 : k; break;
+    }
+}
+/* off-diagonal part of row (T, S) of cell (i,jl,k) applied to the iterate */
+__device__ __forceinline__ void mg_offmul(const TsLev& V, int i, int jl, int k, int64_t c,
+                                          double& at, double& as)
+{
+    const int64_t cs = V.cstr;
+    at = as = 0.0;
+#pragma unroll
+    for (int q = 0; q < 6; q++) {
+        int ii = i, jj = jl, kk = k;
+        mg_nbc(V, q, ii, jj, kk);
+        const int64_t nc = mg_cell(V, ii, jj, kk);
+        at += V.off[(int64_t)q * cs + c] * V.z[nc];
+        as += V.off[(int64_t)(8 + q) * cs + c] * V.z[cs + nc];
+        if (q == 4) {
+            at += V.off[6 * cs + c] * V.z[cs + nc];
+            as += V.off[14 * cs + c] * V.z[nc];
+        } else if (q == 5) {
+            at += V.off[7 * cs + c] * V.z[cs + nc];
+            as += V.off[15 * cs + c] * V.z[nc];
+        }
+    }
+}
+/* colour of water column (i, jl): parity of i + j (global j on level 0); on a periodic
+ * level with odd n the wrap pair (n-1, 0) would share a colour, so column n-1 gets 2 / 3 */
+__host__ __device__ __forceinline__ int mg_ncolour(const TsLev& V) { return (V.periodic && (V.n & 1)) ? 4 : 2; }
+__device__ __forceinline__ int mg_lcolour(const TsLev& V, int i, int jl)
+{
+    if (V.periodic && (V.n & 1) && i == V.n - 1) return 2 + ((jl + V.jpar) & 1);
+    return (i + jl + V.jpar) & 1;
+}
+/* g-th owned column of a colour: row jl holds i = 2h + ((colour + jl + jpar) & 1), h <
+ * ceil(n'/2), n' = n - 1 on an odd periodic level (whose last column has colour 2 or 3).
+ * hr (bands' level 0): the rows run from -1 to mb, the halo row -1 when hr & 1, mb when
+ * hr & 2 (the parity of a negative jl is that of the global row too) */
+__device__ __forceinline__ bool mg_column(const TsLev& V, int colour, int g, int& i, int& jl, int hr = 0)
+{
+    const int np = (V.periodic && (V.n & 1)) ? V.n - 1 : V.n;
+    const int rows = V.mb + (hr ? 2 : 0), j0 = hr ? -1 : 0;
+    if (colour < 2) {
+        const int per_row = (np + 1) / 2;
+        if (g >= per_row * rows) return false;
+        jl = g / per_row + j0;
+        i = 2 * (g % per_row) + ((colour + jl + V.jpar) & 1);
+    } else {
+        if (g >= rows) return false;
+        jl = g + j0;
+        i = V.n - 1;
+        if (((jl + V.jpar) & 1) != colour - 2) return false;
+    }
+    if ((jl < 0 && !(hr & 1)) || (jl >= V.mb && !(hr & 2))) return false;
+    return i < np || colour >= 2;
+}
+__host__ __device__ __forceinline__ int64_t mg_columns_of(const TsLev& V, int colour, int hr = 0)
+{
+    const int np = (V.periodic && (V.n & 1)) ? V.n - 1 : V.n;
+    const int rows = V.mb + (hr ? 2 : 0);
+    return colour < 2 ? (int64_t)((np + 1) / 2) * rows : rows;
+}
+
+/* Line solve of one column, lane = level k (< l when on): g = A'^-1 r, then the forward
+ * recurrence dp_k = F_k dp_{k-1} + g_k and the backward x_k = dp_k - Cp_k x_{k+1} as affine
+ * Hillis-Steele scans over the P lanes (log2 P shuffle steps of 2x2 algebra each, no
+ * division: the pivots were inverted at set-up).  The factor loads are issued first. */
+/* the 12 line factors of a lane (0 when !on), loadable ahead of the right-hand side */
+struct LineFac {
+    double a0, a1, a2, a3, i0, i1, i2, i3, q0, q1, q2, q3;
+};
+__device__ __forceinline__ LineFac line_fac(const double* __restrict__ f, int64_t cs, bool on)
+{
+    LineFac F{};
+    if (on) {
+        F.a0 = f[0]; F.a1 = f[cs]; F.a2 = f[2 * cs]; F.a3 = f[3 * cs];
+        F.i0 = f[4 * cs]; F.i1 = f[5 * cs]; F.i2 = f[6 * cs]; F.i3 = f[7 * cs];
+        F.q0 = -f[8 * cs]; F.q1 = -f[9 * cs]; F.q2 = -f[10 * cs]; F.q3 = -f[11 * cs];
+    }
+    return F;
+}
+template <int P>
+__device__ __forceinline__ void line_run(const LineFac& F, int k, double rt, double rs, double& xt, double& xs);
+template <int P>
+__device__ __forceinline__ void line_solve(const double* __restrict__ f, int64_t cs, bool on, int k,
+                                           double rt, double rs, double& xt, double& xs)
+{
+    line_run<P>(line_fac(f, cs, on), k, rt, rs, xt, xs);
+}
+template <int P>
+__device__ __forceinline__ void line_run(const LineFac& F, int k, double rt, double rs, double& xt, double& xs)
+{
+    double a0 = F.a0, a1 = F.a1, a2 = F.a2, a3 = F.a3;
+    const double i0 = F.i0, i1 = F.i1, i2 = F.i2, i3 = F.i3;
+    double q0 = F.q0, q1 = F.q1, q2 = F.q2, q3 = F.q3;
+    double ct = i0 * rt + i1 * rs, cv = i2 * rt + i3 * rs;
+#pragma unroll
+    for (int d = 1; d < P; d <<= 1) {
+        const double b0 = __shfl_up(a0, d, P), b1 = __shfl_up(a1, d, P);
+        const double b2 = __shfl_up(a2, d, P), b3 = __shfl_up(a3, d, P);
+        const double dt = __shfl_up(ct, d, P), dv = __shfl_up(cv, d, P);
+        if (k >= d) {
+            const double nt = ct + (a0 * dt + a1 * dv), nv = cv + (a2 * dt + a3 * dv);
+            const double n0 = a0 * b0 + a1 * b2, n1 = a0 * b1 + a1 * b3;
+            const double n2 = a2 * b0 + a3 * b2, n3 = a2 * b1 + a3 * b3;
+            ct = nt; cv = nv; a0 = n0; a1 = n1; a2 = n2; a3 = n3;
+        }
+    }
+#pragma unroll
+    for (int d = 1; d < P; d <<= 1) {
+        const double b0 = __shfl_down(q0, d, P), b1 = __shfl_down(q1, d, P);
+        const double b2 = __shfl_down(q2, d, P), b3 = __shfl_down(q3, d, P);
+        const double dt = __shfl_down(ct, d, P), dv = __shfl_down(cv, d, P);
+        if (k + d < P) {
+            const double nt = ct + (q0 * dt + q1 * dv), nv = cv + (q2 * dt + q3 * dv);
+            const double n0 = q0 * b0 + q1 * b2, n1 = q0 * b1 + q1 * b3;
+            const double n2 = q2 * b0 + q3 * b2, n3 = q2 * b1 + q3 * b3;
+            ct = nt; cv = nv; q0 = n0; q1 = n1; q2 = n2; q3 = n3;
+        }
+    }
+    xt = ct;
+    xs = cv;
+}
+
+/* z-line relaxation of one colour: every column of it solves its 2x2-block tridiagonal T/S
+ * system along k with the horizontal couplings taken from the current iterate.  corr: the
+ * first post-smoothing colour launch, neighbours not yet relaxed in this sweep (smaller
+ * colour) read with their aggregate's coarse correction C.z added.  zout (level 0, final
+ * sweep): the active T/S rows of the preconditioner output (ext layout) get the result. */
+/* the line solve of column (i, jl) of the given colour from the current iterate (level k of
+ * this lane; on: k < l); corr: neighbours of a smaller colour read with their aggregate's
+ * coarse correction C.z added.  Returns the cell index (0 when !on). */
+template <int P>
+__device__ __forceinline__ int64_t zl_col(const TsLev& V, int i, int jl, int k, bool on, int colour,
+                                          const TsLev& C, int corr, double& xt, double& xs)
+{
+    const int64_t cs = V.cstr;
+    int64_t c = 0;
+    double rt = 0.0, rs = 0.0;
+    if (on) {
+        c = mg_cell(V, i, jl, k);
+        rt = V.b[c];
+        rs = V.b[cs + c];
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            int ii = i, jj = jl, kk = k;
+            mg_nbc(V, q, ii, jj, kk);
+            const int64_t nc = mg_cell(V, ii, jj, kk);
+            double zt = V.z[nc], zs = V.z[cs + nc];
+            if (corr && mg_lcolour(V, ii, jj) < colour) {
+                const int64_t p = mg_cell(C, ii >> 1, jj >> 1, k);
+                zt += C.z[p];
+                zs += C.z[C.cstr + p];
+            }
+            rt -= V.off[(int64_t)q * cs + c] * zt;
+            rs -= V.off[(int64_t)(8 + q) * cs + c] * zs;
+        }
+    }
+    line_solve<P>(V.fac + c, cs, on, k, rt, rs, xt, xs);
+    return c;
+}
+
+template <int P>
+__device__ __forceinline__ void zl_one(const TsLev& V, int colour, int g, int k, const TsLev& C, int corr,
+                                       double* __restrict__ zout, int hr)
+{
+    int i, jl;
+    if (!mg_column(V, colour, g, i, jl, hr)) return;       /* whole column groups exit */
+    const int64_t cs = V.cstr;
+    const bool on = k < V.l;
+    double xt, xs;
+    const int64_t c = zl_col<P>(V, i, jl, k, on, colour, C, corr, xt, xs);
+    if (!on) return;
+    V.z[c] = xt;
+    V.z[cs + c] = xs;
+    if (zout && jl >= 0 && jl < V.mb) {
+        const int64_t e = NUN * ((((int64_t)jl + HALO) * V.l + k) * V.n + i);
+        if (V.diag[c] != 0.0) zout[e + TT] = xt;
+        if (V.diag[3 * cs + c] != 0.0) zout[e + SS] = xs;
+    }
+}
+template <int P>
+__global__ void __launch_bounds__(256) k_mg_zl(TsLev V, int colour, TsLev C, int corr,
+                                              double* __restrict__ zout, int hr)
+{
+    zl_one<P>(V, colour, (blockIdx.x * blockDim.x + threadIdx.x) / P, threadIdx.x % P, C, corr, zout, hr);
+}
+
+/* Restriction F -> C (coarse rhs = sum of the children's residuals, fixed order
+ * (c00 + c10) + (c01 + c11)) and, when relax, the coarse level's colour-0 lines from the
+ * zero iterate (zero neighbours), the other coarse cells' iterate set to 0.  P lanes per
+ * coarse column (lane = level k), every lane reads its four children's level k.
+ * shortcut: F was relaxed once, colour 0 then 1, from a zero iterate, so the residual of
+ * colour 1 is 0 and that of colour 0 is -H z (its horizontal neighbours). */
+template <int P>
+__device__ __forceinline__ void rc_one(const TsLev& F, const TsLev& C, int g, int k, int shortcut, int relax)
+{
+    if (g >= C.n * C.mb) return;
+    const int I = g % C.n, J = g / C.n;
+    const bool on = k < C.l;
+    const int64_t fs = F.cstr, cs = C.cstr;
+    const int64_t t = on ? mg_cell(C, I, J, k) : 0;
+    double bt = 0.0, bs = 0.0;
+    if (shortcut) {
+        /* the two colour-0 children (a + b + jpar even), clamped into the level and weighted
+         * 0 outside it, so that all their loads issue at once; (c00 + c10) + (c01 + c11)
+         * with the colour-1 terms 0 is their plain sum */
+        double rr[2][2];
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            const int a = h ? 1 - F.jpar : F.jpar, b = h;
+            const int i0 = 2 * I + a, j0 = 2 * J + b;
+            const bool in = on && i0 < F.n && j0 < F.mb;
+            const int i = min(i0, F.n - 1), jl = min(j0, F.mb - 1), kc = on ? k : 0;
+            const int64_t c = mg_cell(F, i, jl, kc);
+            double at = 0.0, as = 0.0;
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                int ii = i, jj = jl, kk = kc;
+                mg_nbc(F, q, ii, jj, kk);
+                const int64_t nc = mg_cell(F, ii, jj, kk);
+                at += F.off[(int64_t)q * fs + c] * F.z[nc];
+                as += F.off[(int64_t)(8 + q) * fs + c] * F.z[fs + nc];
+            }
+            rr[h][0] = in ? -at : 0.0;
+            rr[h][1] = in ? -as : 0.0;
+        }
+        bt = rr[0][0] + rr[1][0];
+        bs = rr[0][1] + rr[1][1];
+    } else if (on) {
+        double r[4][2] = {{0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}};
+#pragma unroll
+        for (int ch = 0; ch < 4; ch++) {
+            const int i = 2 * I + (ch & 1), jl = 2 * J + (ch >> 1);
+            if (i >= F.n || jl >= F.mb) continue;
+            const int64_t c = mg_cell(F, i, jl, k);
+            double at, as;
+            mg_offmul(F, i, jl, k, c, at, as);
+            const double zt = F.z[c], zs = F.z[fs + c];
+            at += F.diag[c] * zt + F.diag[fs + c] * zs;
+            as += F.diag[2 * fs + c] * zt + F.diag[3 * fs + c] * zs;
+            r[ch][0] = F.b[c] - at;
+            r[ch][1] = F.b[fs + c] - as;
+        }
+        bt = (r[0][0] + r[1][0]) + (r[2][0] + r[3][0]);
+        bs = (r[0][1] + r[1][1]) + (r[2][1] + r[3][1]);
+    }
+    if (on) {
+        C.b[t] = bt;
+        C.b[cs + t] = bs;
+    }
+    if (!relax) return;
+    if (mg_lcolour(C, I, J) == 0) {
+        double xt, xs;
+        line_solve<P>(C.fac + t, cs, on, k, bt, bs, xt, xs);
+        if (on) {
+            C.z[t] = xt;
+            C.z[cs + t] = xs;
+        }
+    } else if (on) {
+        C.z[t] = 0.0;
+        C.z[cs + t] = 0.0;
+    }
+}
+template <int P>
+__global__ void __launch_bounds__(256) k_mg_rc(TsLev F, TsLev C, int shortcut, int relax)
+{
+    rc_one<P>(F, C, (blockIdx.x * blockDim.x + threadIdx.x) / P, threadIdx.x % P, shortcut, relax);
+}
+
+/* ---- fused coarse-level visits (two colours, no halos, one sweep): one launch per 2 x 2
+ * aggregate instead of two dependent launches, each workgroup recomputing the colour-1
+ * lines its aggregate's colour-0 cells border (10 line solves for 2 + 2 outputs; the
+ * coarse levels are latency-bound, their arrays L2-resident).  Groups of P lanes: g < 8
+ * the line of neighbour q = g & 3 of colour-0 child h = g >> 2, g = 8, 9 the aggregate's
+ * own colour-1 children.  The arithmetic is that of the unfused launches, operation for
+ * operation (the sums in the same order), so both give the same iterates. */
+template <int P>
+__device__ __forceinline__ void mg_child0(const TsLev& F, int I, int J, int h, int& i, int& jl, bool& in)
+{
+    const int a = h ? 1 - F.jpar : F.jpar;          /* (a + h + jpar) even: colour 0 */
+    in = 2 * I + a < F.n && 2 * J + h < F.mb;
+    i = min(2 * I + a, F.n - 1);
+    jl = min(2 * J + h, F.mb - 1);
+}
+
+/* down leg at level F (first visit, colour 0 relaxed from zero): colour-1 lines, the
+ * restriction of the residual (zero on colour 1, -H z on colour 0: k_mg_rc's shortcut) and,
+ * when relax, the coarse level's colour-0 lines from zero -- k_mg_zl(colour 1) + k_mg_rc */
+template <int P>
+__global__ void __launch_bounds__(10 * P) k_mg_dn(TsLev F, TsLev C, int relax)
+{
+    __shared__ double xv[8][2][P];
+    const int g = threadIdx.x / P, k = threadIdx.x % P;
+    const int I = blockIdx.x % C.n, J = blockIdx.x / C.n;
+    const bool on = k < F.l;
+    const int64_t fs = F.cstr, cs = C.cstr;
+    const int64_t t = on ? mg_cell(C, I, J, k) : 0;
+    /* group 0's operands of the restriction and the coarse line, loaded before the lines */
+    double po[2][8];
+    LineFac cf{};
+    if (g == 0) {
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            int i, jl;
+            bool in;
+            mg_child0<P>(F, I, J, h, i, jl, in);
+            const int64_t c = mg_cell(F, i, jl, on ? k : 0);
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                po[h][q] = F.off[(int64_t)q * fs + c];
+                po[h][4 + q] = F.off[(int64_t)(8 + q) * fs + c];
+            }
+        }
+        cf = line_fac(C.fac + t, cs, on && relax && mg_lcolour(C, I, J) == 0);
+    }
+    if (g < 8) {
+        const int h = g >> 2, q = g & 3;
+        int i, jl;
+        bool in;
+        mg_child0<P>(F, I, J, h, i, jl, in);
+        double xt = 0.0, xs = 0.0;
+        if (in) {
+            int ii = i, jj = jl, kk = on ? k : 0;
+            mg_nbc(F, q, ii, jj, kk);
+            if (ii == i && jj == jl) {                 /* clamped: the child itself, weight 0 */
+                if (on) {
+                    const int64_t c = mg_cell(F, i, jl, k);
+                    xt = F.z[c];
+                    xs = F.z[fs + c];
+                }
+            } else {
+                zl_col<P>(F, ii, jj, k, on, 1, F, 0, xt, xs);
+            }
+        }
+        xv[g][0][k] = xt;
+        xv[g][1][k] = xs;
+    } else {
+        const int h = g - 8, a = h ? F.jpar : 1 - F.jpar;   /* colour 1 */
+        const int i = 2 * I + a, jl = 2 * J + h;
+        if (i < F.n && jl < F.mb) {
+            double xt, xs;
+            const int64_t c = zl_col<P>(F, i, jl, k, on, 1, F, 0, xt, xs);
+            if (on) {
+                F.z[c] = xt;
+                F.z[fs + c] = xs;
+            }
+        }
+    }
+    __syncthreads();
+    if (g != 0) return;
+    double rr[2][2];
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        int i, jl;
+        bool in;
+        mg_child0<P>(F, I, J, h, i, jl, in);
+        double at = 0.0, as = 0.0;
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            at += po[h][q] * xv[4 * h + q][0][k];
+            as += po[h][4 + q] * xv[4 * h + q][1][k];
+        }
+        rr[h][0] = (on && in) ? -at : 0.0;
+        rr[h][1] = (on && in) ? -as : 0.0;
+    }
+    const double bt = rr[0][0] + rr[1][0], bs = rr[0][1] + rr[1][1];
+    if (on) {
+        C.b[t] = bt;
+        C.b[cs + t] = bs;
+    }
+    if (!relax) return;
+    if (mg_lcolour(C, I, J) == 0) {
+        double xt, xs;
+        line_run<P>(cf, k, bt, bs, xt, xs);
+        if (on) {
+            C.z[t] = xt;
+            C.z[cs + t] = xs;
+        }
+    } else if (on) {
+        C.z[t] = 0.0;
+        C.z[cs + t] = 0.0;
+    }
+}
+
+/* up leg at level F (one sweep, colours 1 then 0): the colour-1 lines with the coarse
+ * correction C.z added to their colour-0 neighbours, then the colour-0 lines from the new
+ * colour-1 values -- k_mg_zl(1, corr) + k_mg_zl(0); the result goes to zu (not F.z, which
+ * the neighbouring workgroups still read) */
+template <int P>
+__global__ void __launch_bounds__(10 * P) k_mg_up(TsLev F, TsLev C, double* __restrict__ zu)
+{
+    __shared__ double xv[8][2][P];
+    const int g = threadIdx.x / P, k = threadIdx.x % P;
+    const int I = blockIdx.x % C.n, J = blockIdx.x / C.n;
+    const bool on = k < F.l;
+    const int64_t fs = F.cstr;
+    /* groups 0, 1: their colour-0 child's operands, loaded before the colour-1 lines */
+    int64_t c0 = 0;
+    bool in0 = false;
+    double b0t = 0.0, b0s = 0.0, po[8];
+    LineFac ff{};
+    if (g < 2) {
+        int i, jl;
+        mg_child0<P>(F, I, J, g, i, jl, in0);
+        if (in0 && on) {
+            c0 = mg_cell(F, i, jl, k);
+            b0t = F.b[c0];
+            b0s = F.b[fs + c0];
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                po[q] = F.off[(int64_t)q * fs + c0];
+                po[4 + q] = F.off[(int64_t)(8 + q) * fs + c0];
+            }
+        }
+        ff = line_fac(F.fac + c0, fs, in0 && on);
+    }
+    if (g < 8) {
+        const int h = g >> 2, q = g & 3;
+        int i, jl;
+        bool in;
+        mg_child0<P>(F, I, J, h, i, jl, in);
+        double xt = 0.0, xs = 0.0;
+        if (in) {
+            int ii = i, jj = jl, kk = on ? k : 0;
+            mg_nbc(F, q, ii, jj, kk);
+            if (ii == i && jj == jl) {                 /* clamped: the child's old value, weight 0 */
+                if (on) {
+                    const int64_t c = mg_cell(F, i, jl, k);
+                    xt = F.z[c];
+                    xs = F.z[fs + c];
+                }
+            } else {
+                zl_col<P>(F, ii, jj, k, on, 1, C, 1, xt, xs);
+            }
+        }
+        xv[g][0][k] = xt;
+        xv[g][1][k] = xs;
+    } else {
+        const int h = g - 8, a = h ? F.jpar : 1 - F.jpar;
+        const int i = 2 * I + a, jl = 2 * J + h;
+        if (i < F.n && jl < F.mb) {
+            double xt, xs;
+            const int64_t c = zl_col<P>(F, i, jl, k, on, 1, C, 1, xt, xs);
+            if (on) {
+                zu[c] = xt;
+                zu[fs + c] = xs;
+            }
+        }
+    }
+    __syncthreads();
+    if (g >= 2 || !in0) return;                        /* whole groups */
+    /* colour-0 child h = g: its line from the four new colour-1 neighbours (k_mg_zl colour 0) */
+    const int h = g;
+    double rt = b0t, rs = b0s;
+    if (on) {
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            rt -= po[q] * xv[4 * h + q][0][k];
+            rs -= po[4 + q] * xv[4 * h + q][1][k];
+        }
+    }
+    double xt, xs;
+    line_run<P>(ff, k, rt, rs, xt, xs);
+    if (on) {
+        zu[c0] = xt;
+        zu[fs + c0] = xs;
+    }
+}
+
+/* Level-0 entry: the T/S right-hand side rr_TS - A_TS,D z_D of a tile of TI columns of one
+ * latitude row (Jacobian slots read along i, coalesced; identity-row columns skipped by
+ * the slot bitmask), transposed through LDS into the k-contiguous level layout, then the
+ * tile's colour-0 lines relaxed from the zero iterate and the other columns' iterate set
+ * to 0 (one launch instead of rhs + first colour). */
+constexpr int MG_TI = 16;
+template <int P>
+__global__ void __launch_bounds__(256) k_mg_entry(const double* __restrict__ val, const uint8_t* __restrict__ knP,
+                                                 const uint64_t* __restrict__ kmask,
+                                                 const double* __restrict__ rr, const double* __restrict__ z,
+                                                 Lay L, TsLev V)
+{
+    LAY_ALIASES;
+    __shared__ double sb[2][64][MG_TI + 1];
+    const int nx = L.nx;
+    const int tiles = (nx + MG_TI - 1) / MG_TI;
+    const int jl = blockIdx.x / tiles, i0 = (blockIdx.x % tiles) * MG_TI;
+    const int j = L.jb0 + jl;
+    const SubLay X = sub_of(L);
+    for (int e = threadIdx.x; e < 2 * l * MG_TI; e += blockDim.x) {
+        const int R = TT + e / (l * MG_TI);
+        const int k = (e / MG_TI) % l, ii = e % MG_TI, i = i0 + ii;
+        double acc = 0.0;
+        if (i < nx) {
+            const int64_t lc = ((int64_t)jl * l + k) * nx + i;
+            const int64_t cell = L.own0 + lc;
+            const int64_t row = PL(cell, R);
+            if (!knP[row]) {
+                int nc[3][9];
+                nb_cells(X, i, j, k, nc);
+                const uint64_t kb = kmask[2 * cell + 1];
+                acc = R == TT ? bts_row<TT>(val, z, lc, L.nloc, nc, kb, rr[row], 1, L.ps)
+                              : bts_row<SS>(val, z, lc, L.nloc, nc, kb, rr[row], 1, L.ps);
+            }
+        }
+        sb[R - TT][k][ii] = acc;
+    }
+    __syncthreads();
+    const int grp = threadIdx.x / P, k = threadIdx.x % P, ng = blockDim.x / P;
+    const bool on = k < l;
+    for (int ii = grp; ii < MG_TI; ii += ng) {
+        const int i = i0 + ii;
+        if (i >= nx) break;
+        const int64_t c = on ? mg_cell(V, i, jl, k) : 0;
+        const double bt = on ? sb[0][k][ii] : 0.0, bs = on ? sb[1][k][ii] : 0.0;
+        if (on) {
+            V.b[c] = bt;
+            V.b[V.cstr + c] = bs;
+        }
+        if (mg_lcolour(V, i, jl) == 0) {
+            double xt, xs;
+            line_solve<P>(V.fac + c, V.cstr, on, k, bt, bs, xt, xs);
+            if (on) {
+                V.z[c] = xt;
+                V.z[V.cstr + c] = xs;
+            }
+        } else if (on) {
+            V.z[c] = 0.0;
+            V.z[V.cstr + c] = 0.0;
+        }
+    }
+}
+
+/* fine iterate += coarse correction of its aggregate (active unknowns; level 0 of a band
+ * group only, where the first post-smoothing colour reads neighbours across the band edge) */
+__global__ void k_mg_prolong(TsLev F, TsLev C)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (int64_t)F.n * F.mb * F.l) return;
+    const int k = (int)(t % F.l), i = (int)((t / F.l) % F.n), jl = (int)(t / ((int64_t)F.l * F.n));
+    const int64_t c = mg_cell(F, i, jl, k), p = mg_cell(C, i >> 1, jl >> 1, k);
+    if (F.diag[c] != 0.0) F.z[c] += C.z[p];
+    if (F.diag[3 * F.cstr + c] != 0.0) F.z[F.cstr + c] += C.z[C.cstr + p];
+}
+
+/* level-0 iterate -> z(T, S) of the preconditioner output on the active rows (when the
+ * T/S block was solved before the last dynamics pass, whose defects see z(T, S) = 0) */
+__global__ void k_mg_out(TsLev V, double* __restrict__ zout)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (int64_t)V.n * V.mb * V.l) return;
+    const int k = (int)(t % V.l), i = (int)((t / V.l) % V.n), jl = (int)(t / ((int64_t)V.l * V.n));
+    const int64_t c = mg_cell(V, i, jl, k);
+    const int64_t e = NUN * ((((int64_t)jl + HALO) * V.l + k) * V.n + i);
+    if (V.diag[c] != 0.0) zout[e + TT] = V.z[c];
+    if (V.diag[3 * V.cstr + c] != 0.0) zout[e + SS] = V.z[V.cstr + c];
+}
+
+/* level 0: the compact T/S couplings and 2x2 blocks (ext layout) into the level layout */
+__global__ void k_mg_pack0(const double* __restrict__ tsoff, const double* __restrict__ tsdiag, Lay L,
+                           int64_t next, TsLev V, double* __restrict__ off, double* __restrict__ diag)
+{
+    OWNED_CELL;
+    const int64_t c = mg_cell(V, i - L.ib0, j - L.jb0, k);
+#pragma unroll
+    for (int e = 0; e < 16; e++) off[(int64_t)e * V.cstr + c] = tsoff[(int64_t)e * next + cell];
+#pragma unroll
+    for (int e = 0; e < 4; e++) diag[(int64_t)e * V.cstr + c] = tsdiag[(int64_t)e * next + cell];
+}
+
+/* Galerkin coarse operator: sum of the children's blocks and couplings; couplings inside
+ * the aggregate go to the coarse 2x2 block */
+__global__ void k_mg_galerkin(TsLev F, TsLev C, double* __restrict__ off, double* __restrict__ diag)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (int64_t)C.n * C.mb * C.l) return;
+    const int k = (int)(t % C.l), I = (int)((t / C.l) % C.n), J = (int)(t / ((int64_t)C.l * C.n));
+    const int64_t fs = F.cstr;
+    double o[16], d[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int e = 0; e < 16; e++) o[e] = 0.0;
+    for (int b = 0; b < 2; b++)
+        for (int a = 0; a < 2; a++) {
+            const int i = 2 * I + a, jl = 2 * J + b;
+            if (i >= F.n || jl >= F.mb) continue;
+            const int64_t c = mg_cell(F, i, jl, k);
+            for (int e = 0; e < 4; e++) d[e] += F.diag[(int64_t)e * fs + c];
+            for (int R = 0; R < 2; R++)
+                for (int q = 0; q < 8; q++) {
+                    const double v = F.off[(int64_t)(8 * R + q) * fs + c];
+                    if (v == 0.0) continue;
+                    int ii = i, jj = jl, kk = k;
+                    if (!mg_nb(F, q < 6 ? q : q - 2, ii, jj, kk)) continue;
+                    if (q < 6 && ii >= 0 && ii < F.n && jj >= 0 && jj < F.mb && (ii >> 1) == I && (jj >> 1) == J &&
+                        kk == k)
+                        d[3 * R] += v;                    /* same variable, same aggregate */
+                    else
+                        o[8 * R + q] += v;
+                }
+        }
+    const bool at = d[0] != 0.0, as = d[3] != 0.0;
+    if (!at) { d[1] = d[2] = 0.0; for (int q = 0; q < 8; q++) o[q] = 0.0; }
+    if (!as) { d[1] = d[2] = 0.0; for (int q = 8; q < 16; q++) o[q] = 0.0; }
+    /* the level's layout (a level with an x halo pads its rows) */
+    const int64_t cs = C.cstr, cc = mg_cell(C, I, J, k);
+    for (int e = 0; e < 16; e++) off[(int64_t)e * cs + cc] = o[e];
+    for (int e = 0; e < 4; e++) diag[(int64_t)e * cs + cc] = d[e];
+}
+
+/* z-line factors of every owned column (one thread each, serial block Thomas along k, the
+ * CPU twin's mg_zline arithmetic): A'_k = A_k - B_k Cp_{k-1}, F_k = -A'_k^-1 B_k, Cp_k =
+ * A'_k^-1 C_k; inactive unknowns (zero diagonal) are identity rows whose A'^-1 and F rows
+ * are zeroed, so their line values come out 0 whatever the right-hand side */
+__global__ void k_mg_fac(TsLev V, double* __restrict__ fac)
+{
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= V.n * V.mb) return;
+    const int i = t % V.n, jl = t / V.n;
+    const int64_t cs = V.cstr;
+    double P0 = 0.0, P1 = 0.0, P2 = 0.0, P3 = 0.0;
+    for (int k = 0; k < V.l; k++) {
+        const int64_t c = mg_cell(V, i, jl, k);
+        double Am[4] = {V.diag[c], V.diag[cs + c], V.diag[2 * cs + c], V.diag[3 * cs + c]};
+        double Bm[4] = {V.off[4 * cs + c], V.off[6 * cs + c], V.off[14 * cs + c], V.off[12 * cs + c]};
+        double Cm[4] = {V.off[5 * cs + c], V.off[7 * cs + c], V.off[15 * cs + c], V.off[13 * cs + c]};
+        const bool at = Am[0] != 0.0, as = Am[3] != 0.0;
+        if (!at) { Am[0] = 1.0; Am[1] = Am[2] = 0.0; Bm[0] = Bm[1] = 0.0; Cm[0] = Cm[1] = 0.0; }
+        if (!as) { Am[3] = 1.0; Am[1] = Am[2] = 0.0; Bm[2] = Bm[3] = 0.0; Cm[2] = Cm[3] = 0.0; }
+        if (k == 0) Bm[0] = Bm[1] = Bm[2] = Bm[3] = 0.0;
+        else {
+            const double a0 = Am[0] - (Bm[0] * P0 + Bm[1] * P2), a1 = Am[1] - (Bm[0] * P1 + Bm[1] * P3);
+            const double a2 = Am[2] - (Bm[2] * P0 + Bm[3] * P2), a3 = Am[3] - (Bm[2] * P1 + Bm[3] * P3);
+            Am[0] = a0; Am[1] = a1; Am[2] = a2; Am[3] = a3;
+        }
+        const double det = Am[0] * Am[3] - Am[1] * Am[2];
+        const double qd = det != 0.0 ? 1.0 / det : 0.0;
+        double I0 = Am[3] * qd, I1 = -Am[1] * qd, I2 = -Am[2] * qd, I3 = Am[0] * qd;
+        P0 = I0 * Cm[0] + I1 * Cm[2]; P1 = I0 * Cm[1] + I1 * Cm[3];
+        P2 = I2 * Cm[0] + I3 * Cm[2]; P3 = I2 * Cm[1] + I3 * Cm[3];
+        double F0 = -(I0 * Bm[0] + I1 * Bm[2]), F1 = -(I0 * Bm[1] + I1 * Bm[3]);
+        double F2 = -(I2 * Bm[0] + I3 * Bm[2]), F3 = -(I2 * Bm[1] + I3 * Bm[3]);
+        if (!at) { I0 = I1 = F0 = F1 = 0.0; }
+        if (!as) { I2 = I3 = F2 = F3 = 0.0; }
+        const double v[12] = {F0, F1, F2, F3, I0, I1, I2, I3, P0, P1, P2, P3};
+#pragma unroll
+        for (int e = 0; e < 12; e++) fac[(int64_t)e * cs + c] = v[e];
+    }
+}
+
+}  // namespace
+
+/* ---- T/S multigrid: host side ------------------------------------------------------ */
+/* intermediate levels (1 ..) that carry the x halo under x splits */
+constexpr int MG_XHALO_LEVELS = 99;
+static TsLev mg_view(iemic_ctx* c, int q)
+{
+    BlockGS& gs = c->gs;
+    TsLev V{};
+    V.l = c->l;
+    V.n = gs.mg.n[q];
+    V.mb = gs.mg.m[q];
+    /* subdomains: the level-0 smoother and residual see the neighbours' edge rows and
+     * columns (halo rows / columns in the layout, exchanged before every relaxation); with
+     * an x split the intermediate levels see the neighbours' edge columns too (a cut across
+     * the zonal flow would otherwise make them block Jacobi), the coarsest is
+     * the global problem; colours by the global i + j parity of the level's aggregates, so
+     * that all subdomains relax the same colour in the same launch and a cell's neighbours
+     * across a cut have the other colour; the x wrap only with one x part */
+    const int qc = gs.mg.nlev - 1;
+    V.periodic = c->cfg.periodic && c->npx == 1;
+    V.hj = (q == 0 && c->npy > 1) ? (gs.mg.hr ? 2 : 1) : 0;
+    V.hi = (q < qc && q <= MG_XHALO_LEVELS && c->npx > 1) ? 1 : 0;
+    V.vis = V.hj;
+    V.visi = V.hi;
+    V.jpar = gs.mg.par[q];
+    V.cstr = (int64_t)(V.mb + 2 * V.hj) * (V.n + 2 * V.hi) * V.l;
+    V.off = gs.mg.off[q].p;
+    V.diag = gs.mg.diag[q].p;
+    V.fac = gs.mg.fac[q].p;
+    V.b = gs.mg.b[q].p;
+    V.z = gs.mg.z[q].p;
+    return V;
+}
+
+/* Gauss-Jordan inverse with partial pivoting (host, large coarsest levels); unknowns
+ * without any coupling (inactive) get an identity row */
+static void dense_inverse(std::vector<double>& A, int N, std::vector<double>& X)
+{
+    X.assign((size_t)N * N, 0.0);
+    for (int i = 0; i < N; i++) {
+        X[(size_t)i * N + i] = 1.0;
+        bool any = false;
+        for (int j = 0; j < N; j++) any |= A[(size_t)i * N + j] != 0.0;
+        if (!any) A[(size_t)i * N + i] = 1.0;
+    }
+    for (int k = 0; k < N; k++) {
+        int p = k;
+        for (int i = k + 1; i < N; i++)
+            if (std::fabs(A[(size_t)i * N + k]) > std::fabs(A[(size_t)p * N + k])) p = i;
+        if (p != k)
+            for (int j = 0; j < N; j++) {
+                std::swap(A[(size_t)p * N + j], A[(size_t)k * N + j]);
+                std::swap(X[(size_t)p * N + j], X[(size_t)k * N + j]);
+            }
+        const double d = A[(size_t)k * N + k];
+        const double q = d != 0.0 ? 1.0 / d : 0.0;
+        for (int j = 0; j < N; j++) {
+            A[(size_t)k * N + j] *= q;
+            X[(size_t)k * N + j] *= q;
+        }
+        for (int i = 0; i < N; i++) {
+            if (i == k) continue;
+            const double f = A[(size_t)i * N + k];
+            if (f == 0.0) continue;
+            for (int j = 0; j < N; j++) {
+                A[(size_t)i * N + j] -= f * A[(size_t)k * N + j];
+                X[(size_t)i * N + j] -= f * X[(size_t)k * N + j];
+            }
+        }
+    }
+}
+
+/* decode of a coarse-level cell index t = (jl n + i) l + k */
+static inline void mg_decode(int64_t t, int n, int l, int& i, int& jl, int& k)
+{
+    k = (int)(t % l);
+    i = (int)((t / l) % n);
+    jl = (int)(t / ((int64_t)l * n));
+}
+
+/* the global coarse grid: rank (px, py)'s coarsest grid at column offset ioff[px], row offset
+ * joff[py] of GX x GY cells; band half-widths and row width of its matrix */
+struct MgGlob {
+    std::vector<int> ioff, joff;
+    int GX, GY, I0, J0, NG, bl, bu, W;
+};
+static int mg_global_grid(iemic_ctx* c, MgGlob& G)
+{
+    BlockGS& gs = c->gs;
+    const int P = c->nranks, l = c->l, qc = gs.mg.nlev - 1;
+    int rc;
+    /* coarsest columns / rows of every rank: offsets of its rank column / row */
+    std::vector<double> dims(2 * P, 0.0);
+    dims[2 * c->rank] = gs.mg.n[qc];
+    dims[2 * c->rank + 1] = gs.mg.m[qc];
+    {
+        DevBuf<double> rb;
+        if (rb.alloc(2 * P)) return IEMIC_ENOMEM;
+        if ((rc = h2d(c, rb.p, dims.data(), sizeof(double) * 2 * P))) return rc;
+        if ((rc = allreduce_sum(c, rb.p, 2 * P))) return rc;
+        if ((rc = d2h(c, dims.data(), rb.p, sizeof(double) * 2 * P))) return rc;
+    }
+    G.ioff.assign(c->npx + 1, 0);
+    G.joff.assign(c->npy + 1, 0);
+    for (int px = 0; px < c->npx; px++) G.ioff[px + 1] = G.ioff[px] + (int)dims[2 * px];
+    for (int py = 0; py < c->npy; py++) G.joff[py + 1] = G.joff[py] + (int)dims[2 * (py * c->npx) + 1];
+    G.GX = G.ioff[c->npx];
+    G.GY = G.joff[c->npy];
+    G.I0 = G.ioff[c->px];
+    G.J0 = G.joff[c->py];
+    G.NG = 2 * G.GX * G.GY * l;
+    G.bl = 2 * l * G.GX + 1;
+    G.bu = G.bl;
+    G.W = 2 * G.bl + G.bu + 1;
+    return 0;
+}
+
+/* this rank's rows of the global band matrix H; *ok = false: an entry outside the band */
+static int mg_global_rows(iemic_ctx* c, const MgGlob& G, const std::vector<double>& off,
+                          const std::vector<double>& dg, std::vector<double>& H, bool* okp)
+{
+    BlockGS& gs = c->gs;
+    const int l = c->l, qc = gs.mg.nlev - 1;
+    const int nc = gs.mg.n[qc], cm = gs.mg.m[qc], mb = c->jb1 - c->jb0;
+    const int64_t ncl = (int64_t)nc * cm * l;
+    int rc;
+    H.assign((size_t)G.NG * G.W, 0.0);
+    const bool wrap = c->cfg.periodic != 0;
+    auto gidx = [&](int J, int I, int k, int var) { return 2 * ((J * G.GX + I) * l + k) + var; };
+    auto gwrap = [&](int I) { return I < 0 ? I + G.GX : (I >= G.GX ? I - G.GX : I); };
+    auto add = [&](int row, int col, double v) {
+        const int d = col - row;
+        if (d < -G.bl || d > G.bu) return false;
+        H[(size_t)row * G.W + (d + G.bl)] += v;
+        return true;
+    };
+    bool ok = true;
+    const bool lwrap = wrap && c->npx == 1;           /* the local level wraps in x */
+    for (int64_t t = 0; t < ncl; t++) {
+        int i, jl, k;
+        mg_decode(t, nc, l, i, jl, k);
+        for (int R = 0; R < 2; R++) {
+            const int row = gidx(G.J0 + jl, G.I0 + i, k, R);
+            ok &= add(row, gidx(G.J0 + jl, G.I0 + i, k, R), dg[(3 * R) * ncl + t]);
+            ok &= add(row, gidx(G.J0 + jl, G.I0 + i, k, 1 - R), dg[(1 + R) * ncl + t]);
+            for (int qq = 0; qq < 8; qq++) {
+                const double v = off[(8 * R + qq) * ncl + t];
+                if (v == 0.0) continue;
+                int ii = i, jj = jl, kk = k;
+                switch (qq < 6 ? qq : qq - 2) {
+                case 0: ii--; break;
+                case 1: ii++; break;
+                case 2: jj--; break;
+                case 3: jj++; break;
+                case 4: kk--; break;
+                default: kk++; break;
+                }
+                if (jj < 0 || jj >= cm || kk < 0 || kk >= l) continue;
+                if (ii < 0 || ii >= nc) {
+                    if (!lwrap) continue;
+                    ii = (ii + nc) % nc;
+                }
+                ok &= add(row, gidx(G.J0 + jj, G.I0 + ii, kk, qq < 6 ? R : 1 - R), v);
+            }
+        }
+    }
+    /* cross-subdomain couplings: level-0 T/S couplings of the first / last latitude row (-j /
+     * +j) and the first / last column (-i / +i), summed into the edge aggregates */
+    {
+        const int64_t nx = c->nx, slab = (int64_t)l * nx;
+        std::vector<double> e((size_t)slab * mb);
+        for (int dir = 0; dir < 4; dir++) {
+            if (c->nb[dir] < 0) continue;
+            const int q = dir == 0 ? 0 : dir == 1 ? 1 : dir == 2 ? 2 : 3;   /* -i, +i, -j, +j */
+            for (int R = 0; R < 2; R++) {
+                /* the owned rows of coupling q of row R (ext layout: one slab) */
+                const double* src = gs.sw.tsoff.p + (int64_t)(R * 8 + q) * c->next + c->own0;
+                if ((rc = d2h(c, e.data(), src, sizeof(double) * e.size()))) return rc;
+                for (int jl = 0; jl < mb; jl++)
+                    for (int k = 0; k < l; k++)
+                        for (int il = 0; il < nx; il++) {
+                            const bool edge = dir == 0 ? il == 0 : dir == 1 ? il == nx - 1 : dir == 2 ? jl == 0 : jl == mb - 1;
+                            if (!edge) continue;
+                            const double v = e[((int64_t)jl * l + k) * nx + il];
+                            if (v == 0.0) continue;
+                            const int Is = G.I0 + (il >> qc), Js = G.J0 + (jl >> qc);
+                            const int Id = dir == 0 ? gwrap(G.I0 - 1) : dir == 1 ? gwrap(G.ioff[c->px + 1]) : Is;
+                            const int Jd = dir == 2 ? G.J0 - 1 : dir == 3 ? G.joff[c->py + 1] : Js;
+                            ok &= add(gidx(Js, Is, k, R), gidx(Jd, Id, k, R), v);
+                        }
+            }
+        }
+    }
+    *okp = ok;
+    if (!ok) return 0;
+    /* own rows without entries (inactive unknowns) become identity rows */
+    for (int jl = 0; jl < cm; jl++)
+        for (int i = 0; i < nc; i++)
+            for (int k = 0; k < l; k++)
+                for (int R = 0; R < 2; R++) {
+                    const int row = gidx(G.J0 + jl, G.I0 + i, k, R);
+                    bool any = false;
+                    for (int d = 0; d < G.W; d++) any |= H[(size_t)row * G.W + d] != 0.0;
+                    if (!any) H[(size_t)row * G.W + G.bl] = 1.0;
+                }
+    return 0;
+}
+
+/* Subdomains: the coarsest T/S level as one global problem.  The ranks' coarsest grids
+ * tile a GX x GY coarse grid (rank (px, py) at column offset ioff[px], row offset joff[py]);
+ * unknown (J, I, k, var) is 2((J GX + I) l + k) + var, a band matrix of half-width
+ * 2 l GX + 1 (+ the periodic wrap inside a row).  Every rank writes its own rows -- its
+ * local coarsest operator plus the couplings of its edge aggregates to the neighbours'
+ * edge aggregates, taken from the level-0 couplings across the subdomain edges (the
+ * Galerkin sum of piecewise-constant aggregates) -- the rows are summed over the ranks,
+ * and every rank factorises and inverts the whole matrix (band_lu.hip). */
+static int mg_global_setup(iemic_ctx* c, const std::vector<double>& off, const std::vector<double>& dg)
+{
+    BlockGS& gs = c->gs;
+    gs.mg.glob = 0;
+    if (c->nranks <= 1 || c->l > 64) return 0;
+    int rc;
+    MgGlob G;
+    if ((rc = mg_global_grid(c, G))) return rc;
+    const int NG = G.NG, bl = G.bl, bu = G.bu, W = G.W;
+    {
+        /* LDS of the band kernels (same rules as the Schur band) */
+        const size_t lb = sizeof(double) * ((size_t)(BAND_NBP + bl) * (BAND_NBP + 1) + (size_t)BAND_NBP * (bl + bu));
+        const size_t li = sizeof(double) * (size_t)(std::max(bl + BAND_NBP + 1, bl + bu + 1) + 2 * BAND_NBP) * 16;
+        if (lb > 150 * 1024 || li > 150 * 1024 || (int64_t)NG * W > INT32_MAX) return 0;   /* stay local */
+    }
+    std::vector<double> H;
+    bool ok = true;
+    if ((rc = mg_global_rows(c, G, off, dg, H, &ok))) return rc;
+    if (!ok) return 0;                        /* outside the assumed band: stay local */
+    const size_t npan = (size_t)(NG + BAND_NBP - 1) / BAND_NBP;
+    if (gs.mg.gband.n < (size_t)NG * W) {
+        if (gs.mg.gband.alloc((size_t)NG * W) || gs.mg.gX.alloc((size_t)NG * NG) ||
+            gs.mg.gvec.alloc(NG) || gs.mg.gtmp.alloc(NG) || gs.mg.gpiv.alloc(NG) ||
+            gs.mg.ginfo.alloc(1) || gs.mg.gcols.alloc(NG) ||
+            gs.mg.glpan.alloc(npan * (BAND_NBP + bl) * BAND_NBP))
+            return IEMIC_ENOMEM;
+        std::vector<int> cols(NG);
+        for (int q = 0; q < NG; q++) cols[q] = q;
+        if ((rc = h2d(c, gs.mg.gcols.p, cols.data(), sizeof(int) * NG))) return rc;
+    }
+    if ((rc = h2d(c, gs.mg.gband.p, H.data(), sizeof(double) * H.size()))) return rc;
+    if ((rc = allreduce_sum(c, gs.mg.gband.p, (int)((size_t)NG * W)))) return rc;
+    int info = 0;
+    if ((rc = band_lu_inverse(c, gs.mg.gband.p, NG, bl, bu, gs.mg.gpiv.p, gs.mg.ginfo.p, gs.mg.glpan.p,
+                              gs.mg.gcols.p, gs.mg.gX.p, &info)))
+        return rc;
+    if (info != 0) return 0;                  /* singular global coarse problem: local */
+    gs.mg.gN = NG;
+    gs.mg.gGX = G.GX;
+    gs.mg.gI0 = G.I0;
+    gs.mg.gJ0 = G.J0;
+    gs.mg.glob = 1;
+    return 0;
+}
+
+/* global index of local coarsest cell t (rank offsets I0, J0 in the GX-wide coarse grid) */
+__device__ __forceinline__ int64_t mg_gq(int64_t t, int nc, int l, int GX, int I0, int J0)
+{
+    const int k = (int)(t % l), i = (int)((t / l) % nc), jl = (int)(t / ((int64_t)l * nc));
+    return 2 * ((((int64_t)J0 + jl) * GX + I0 + i) * l + k);
+}
+/* local coarsest rhs (T block, S block) -> its entries of the global vector */
+__global__ void k_mg_gput(const double* __restrict__ b, int64_t ncl, int nc, int l, int GX, int I0, int J0,
+                          double* __restrict__ g)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= ncl) return;
+    const int64_t q = mg_gq(t, nc, l, GX, I0, J0);
+    g[q] = b[t];
+    g[q + 1] = b[ncl + t];
+}
+/* own rows of the global solution -> local (T block, S block) */
+__global__ void k_mg_gget(const double* __restrict__ y, int64_t ncl, int nc, int l, int GX, int I0, int J0,
+                          double* __restrict__ z)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= ncl) return;
+    const int64_t q = mg_gq(t, nc, l, GX, I0, J0);
+    z[t] = y[q];
+    z[ncl + t] = y[q + 1];
+}
+
+/* the coarsest level's dense operator, row-major A[row * N + col] (one thread per row; the
+ * same entries as the host assembly below), inactive rows -> identity rows */
+__global__ void k_mg_coarse_dense(const double* __restrict__ off, const double* __restrict__ dg, int64_t ncl,
+                                  int cn, int cm, int l, int periodic, double* __restrict__ A)
+{
+    const int64_t rowq = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (rowq >= 2 * ncl) return;
+    const int R = (int)(rowq / ncl);
+    const int64_t t = rowq % ncl;
+    const int64_t N = 2 * ncl;
+    double* Ar = A + rowq * N;
+    const int k = (int)(t % l), i = (int)((t / l) % cn), jl = (int)(t / ((int64_t)l * cn));
+    Ar[R * ncl + t] += dg[(3 * R) * ncl + t];
+    Ar[(1 - R) * ncl + t] += dg[(1 + R) * ncl + t];
+    for (int qq = 0; qq < 8; qq++) {
+        const double v = off[(8 * R + qq) * ncl + t];
+        if (v == 0.0) continue;
+        int ii = i, jj = jl, kk = k;
+        const int dir = qq < 6 ? qq : qq - 2;
+        switch (dir) {
+        case 0: ii--; break;
+        case 1: ii++; break;
+        case 2: jj--; break;
+        case 3: jj++; break;
+        case 4: kk--; break;
+        default: kk++; break;
+        }
+        if (jj < 0 || jj >= cm || kk < 0 || kk >= l) continue;
+        if (ii < 0 || ii >= cn) {
+            if (!periodic) continue;
+            ii = (ii + cn) % cn;
+        }
+        const int64_t nb = ((int64_t)jj * cn + ii) * l + kk;
+        const int var = qq < 6 ? R : 1 - R;
+        Ar[var * ncl + nb] += v;
+    }
+    bool any = false;
+    for (int64_t c = 0; c < N; c++) any |= Ar[c] != 0.0;
+    if (!any) Ar[rowq] = 1.0;
+}
+
+/* the coarsest level's operator as cyclic-reduction blocks over longitudes (one rank, no
+ * halo): block i holds the unknowns (jl l + k) 2 + var of longitude i; D_i couples them
+ * within the longitude (2x2 cell block, -+j, -+k, the T/S cross couplings along k), L_i / R_i
+ * to longitude i -+ 1 (wrapping when periodic).  Inactive unknowns become identity rows.
+ * One thread per (cell, var) row: no write races. */
+__global__ void k_mg_cr_expand(TsLev V, int mc, int periodic, double* __restrict__ D, double* __restrict__ Lb,
+                               double* __restrict__ Rb)
+{
+    const int64_t ncl = (int64_t)V.n * V.mb * V.l;
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= 2 * ncl) return;
+    const int R = (int)(q / ncl);
+    const int64_t t = q % ncl;
+    const int k = (int)(t % V.l), i = (int)((t / V.l) % V.n), jl = (int)(t / ((int64_t)V.l * V.n));
+    const int64_t cs = V.cstr, c = mg_cell(V, i, jl, k);
+    const size_t mm = (size_t)mc * mc;
+    auto idx = [&](int j2, int k2, int var) { return (j2 * V.l + k2) * 2 + var; };
+    const int r = idx(jl, k, R);
+    double* Di = D + (size_t)i * mm;
+    if (V.diag[(int64_t)(3 * R) * cs + c] == 0.0) {
+        Di[r + (size_t)r * mc] = 1.0;
+        return;
+    }
+    Di[r + (size_t)r * mc] += V.diag[(int64_t)(3 * R) * cs + c];
+    Di[r + (size_t)idx(jl, k, 1 - R) * mc] += V.diag[(int64_t)(1 + R) * cs + c];
+    for (int qq = 0; qq < 8; qq++) {
+        const double v = V.off[(int64_t)(8 * R + qq) * cs + c];
+        if (v == 0.0) continue;
+        const int dir = qq < 6 ? qq : qq - 2, var = qq < 6 ? R : 1 - R;
+        int jj = jl, kk = k;
+        double* B = Di;
+        switch (dir) {
+        case 0:
+            if (i == 0 && !periodic) continue;
+            B = Lb + (size_t)i * mm;
+            break;
+        case 1:
+            if (i == V.n - 1 && !periodic) continue;
+            B = Rb + (size_t)i * mm;
+            break;
+        case 2: jj--; break;
+        case 3: jj++; break;
+        case 4: kk--; break;
+        default: kk++; break;
+        }
+        if (jj < 0 || jj >= V.mb || kk < 0 || kk >= V.l) continue;
+        B[r + (size_t)idx(jj, kk, var) * mc] += v;
+    }
+}
+
+/* the whole-problem inverse of the cyclic reduction (row-major, longitude-block order) in
+ * the level's unknown order var ncl + cell, row-major -- what the coarse GEMV applies */
+__global__ void k_mg_cr_perm(const double* __restrict__ T, TsLev V, int N, double* __restrict__ X)
+{
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (int64_t)N * N) return;
+    const int64_t ncl = N / 2;
+    const int rq = (int)(e / N), cq = (int)(e % N);
+    auto cr_of = [&](int u) {
+        const int var = (int)(u / ncl);
+        const int64_t t = u % ncl;
+        const int k = (int)(t % V.l), i = (int)((t / V.l) % V.n), jl = (int)(t / ((int64_t)V.l * V.n));
+        return (int64_t)i * (2 * V.mb * V.l) + (jl * V.l + k) * 2 + var;
+    };
+    X[e] = T[cr_of(rq) * N + cr_of(cq)];
+}
+
+/* level sizes, colour parities and the levels' arrays (first set-up); ts_mg = 0 where the
+ * grid has no coarse level */
+static int mg_levels(iemic_ctx* c)
+{
+    BlockGS& gs = c->gs;
+    const int l = c->l;
+    int rc;
+    /* latitude bands, one sweep: level 0 keeps 2 halo rows (mg_vcycle) */
+    gs.mg.hr = c->npy > 1 && c->npx == 1 && std::max(1, gs.mg.sweeps) == 1;
+    /* coarsen 2x2 horizontally until the level has <= 128 cells (<= 256 unknowns); the
+     * number of levels is that of the largest subdomain, the same on every rank, so the
+     * coarsest grids of the ranks tile the global coarsest problem */
+    int N = (c->n + c->npx - 1) / c->npx, M = (c->m + c->npy - 1) / c->npy, q = 0;
+    int n = c->nx, m = c->jb1 - c->jb0;
+    gs.mg.n[0] = n;
+    gs.mg.m[0] = m;
+    gs.mg.crd = 0;
+    /* one rank: stop at the first level of <= TsMg::CR_CELLS cells that the whole-problem
+     * cyclic reduction takes (blocks of one longitude, 2 m l <= 192 unknowns, >= 2
+     * longitudes): an exact coarse solve, one GEMV per V-cycle instead of the last
+     * levels' ~9 latency-bound launches */
+    auto cr_ok = [&](int nn, int mm) {
+        return c->nranks == 1 && (int64_t)nn * mm * l <= TsMg::CR_CELLS && 2 * mm * l <= 192 && nn >= 2;
+    };
+    while (q + 1 < TsMg::MAX && (q == 0 || (int64_t)N * M * l > 128) && (N > 1 || M > 1) &&
+           !(q > 0 && cr_ok(n, m))) {
+        N = (N + 1) / 2;
+        M = (M + 1) / 2;
+        n = (n + 1) / 2;
+        m = (m + 1) / 2;
+        q++;
+        gs.mg.n[q] = n;
+        gs.mg.m[q] = m;
+    }
+    if (q == 0) {
+        gs.ts_mg = 0;            /* a single water column per band: plain sweeps */
+        return 0;
+    }
+    gs.mg.crd = cr_ok(n, m) && (int64_t)n * m * l > 128 ? 1 : 0;
+    if (gs.mg.crd && (rc = cr_init(c, gs.mg.cr, n, 2 * m * l, c->cfg.periodic, 2 * n * m * l))) return rc;
+    if ((int64_t)n * m * l > 1024) {
+        set_error("block GS: T/S multigrid coarsest level too large");
+        return IEMIC_EINVAL;
+    }
+    gs.mg.nlev = q + 1;
+    /* global offsets of this subdomain's aggregates on every level: the x parts to the
+     * west / the y parts to the south, each coarsened like this one (decomp.h part_of) */
+    for (int lv = 0; lv <= q; lv++) {
+        auto coarse = [&](int v) {
+            for (int t = 0; t < lv; t++) v = (v + 1) / 2;
+            return v;
+        };
+        int io = 0, jo = 0, off, cnt;
+        for (int px = 0; px < c->px; px++) {
+            part_of(c->n, c->npx, px, off, cnt);
+            io += coarse(cnt);
+        }
+        for (int py = 0; py < c->py; py++) {
+            part_of(c->m, c->npy, py, off, cnt);
+            jo += coarse(cnt);
+        }
+        gs.mg.par[lv] = (io + jo) & 1;
+    }
+    for (int lv = 0; lv <= q; lv++) {
+        const size_t cs = (size_t)mg_view(c, lv).cstr;
+        if (gs.mg.off[lv].alloc(16 * cs) || gs.mg.diag[lv].alloc(4 * cs) || gs.mg.fac[lv].alloc(12 * cs) ||
+            gs.mg.b[lv].alloc(2 * cs) || gs.mg.z[lv].alloc(2 * cs) || gs.mg.zu[lv].alloc(2 * cs))
+            return IEMIC_ENOMEM;
+        for (DevBuf<double>* bptr : {&gs.mg.off[lv], &gs.mg.diag[lv], &gs.mg.fac[lv], &gs.mg.b[lv], &gs.mg.z[lv],
+                                     &gs.mg.zu[lv]})
+            HIP_OK(hipMemsetAsync(bptr->p, 0, sizeof(double) * bptr->n, c->stream));
+    }
+    const size_t NC = (size_t)2 * n * m * l;
+    if (gs.mg.cinv.alloc(NC * NC)) return IEMIC_ENOMEM;
+    return 0;
+}
+
+/* level 0 from the compact couplings, the Galerkin chain, the z-line factors; bands: level
+ * 0's of the neighbours' edge rows */
+static int mg_operators(iemic_ctx* c)
+{
+    BlockGS& gs = c->gs;
+    hipStream_t s = c->stream;
+    int rc;
+    {
+        const TsLev V0 = mg_view(c, 0);
+        hipLaunchKernelGGL(k_mg_pack0, dim3(blocks_for(c->nloc)), dim3(256), 0, s, gs.sw.tsoff.p, gs.tsdiag.p,
+                           lay_of(c), c->next, V0, gs.mg.off[0].p, gs.mg.diag[0].p);
+    }
+    for (int q = 1; q < gs.mg.nlev; q++) {
+        TsLev F = mg_view(c, q - 1);
+        const TsLev C = mg_view(c, q);
+        /* the coarse operator keeps the couplings across a cut where the coarse level has a
+         * halo there (x splits, intermediate levels); the coarsest stays local (its global
+         * problem adds the cross couplings itself, mg_global_setup) */
+        F.vis = C.hj;
+        F.visi = C.hi;
+        hipLaunchKernelGGL(k_mg_galerkin, dim3(blocks_for((int64_t)C.n * C.mb * C.l)), dim3(256), 0, s, F, C,
+                           gs.mg.off[q].p, gs.mg.diag[q].p);
+    }
+    for (int q = 0; q + 1 < gs.mg.nlev; q++) {
+        const TsLev V = mg_view(c, q);
+        hipLaunchKernelGGL(k_mg_fac, dim3(blocks_for((int64_t)V.n * V.mb)), dim3(256), 0, s, V, gs.mg.fac[q].p);
+    }
+    HIP_OK(hipGetLastError());
+    if (gs.mg.hr) {
+        /* level 0's couplings, blocks and line factors of the neighbours' edge rows (the
+         * halo-row line solves of mg_vcycle) */
+        const TsLev V = mg_view(c, 0);
+        const int64_t RW = (int64_t)V.n * V.l;
+        const int so = c->nb[2], no = c->nb[3];
+        std::vector<Msg> y;
+        double* const arr[3] = {gs.mg.off[0].p, gs.mg.diag[0].p, gs.mg.fac[0].p};
+        const int ncomp[3] = {16, 4, 12};
+        for (int q = 0; q < 3; q++) {
+            auto row = [&](int jl) { return Seg{arr[q], (V.hj + jl) * RW, ncomp[q], RW, V.cstr}; };
+            if (so >= 0) y.push_back({true, so, row(0)});
+            if (no >= 0) y.push_back({false, no, row(V.mb)});
+            if (no >= 0) y.push_back({true, no, row(V.mb - 1)});
+            if (so >= 0) y.push_back({false, so, row(-1)});
+        }
+        if ((rc = run_msgs(c, y))) return rc;
+    }
+    return 0;
+}
+
+/* coarsest level, one rank (TsMg::crd): cyclic reduction over the level's longitudes */
+static int mg_coarse_cr(iemic_ctx* c, int qc, int64_t ncl, int N)
+{
+    BlockGS& gs = c->gs;
+    hipStream_t s = c->stream;
+    const int l = c->l;
+    int rc;
+    /* cyclic reduction over the level's longitudes: blocks of one longitude, unknown
+     * (jl l + k) 2 + var; the whole problem is its tail, whose explicit inverse is
+     * permuted into the level's (var, cell) order for the coarse GEMV */
+    SchurCR& cr = gs.mg.cr;
+    const int mc = cr.m;
+    const size_t mm = (size_t)mc * mc;
+    HIP_OK(hipMemsetAsync(cr.dlr.p, 0, sizeof(double) * 3 * (size_t)cr.n * mm, s));
+    const TsLev C = mg_view(c, qc);
+    hipLaunchKernelGGL(k_mg_cr_expand, dim3(blocks_for(2 * ncl)), dim3(256), 0, s, C, mc, cr.periodic,
+                       cr.dlr.p, cr.dlr.p + (size_t)cr.n * mm, cr.dlr.p + 2 * (size_t)cr.n * mm);
+    if ((rc = cr_factor_blocks(c, cr))) return rc;
+    if ((rc = cr_check(c, cr))) {
+        set_error("block GS: singular coarsest T/S operator");
+        return rc;
+    }
+    hipLaunchKernelGGL(k_mg_cr_perm, dim3(blocks_for((int64_t)N * N)), dim3(256), 0, s,
+                       (const double*)cr.tinv.p, C, N, gs.mg.cinv.p);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+/* coarsest level of at most 192 unknowns, one rank: its dense operator assembled and
+ * inverted on the device (Gauss-Jordan with pivoting in one workgroup, schur_cr.hip) */
+static int mg_coarse_dev(iemic_ctx* c, int qc, int64_t ncl, int N)
+{
+    BlockGS& gs = c->gs;
+    hipStream_t s = c->stream;
+    const int l = c->l;
+    int rc;
+    DevBuf<double>& A = gs.mg.cdense;
+    if (A.reserve((size_t)N * N)) return IEMIC_ENOMEM;
+    if (!gs.mg.cinfo.p && gs.mg.cinfo.alloc(1)) return IEMIC_ENOMEM;
+    HIP_OK(hipMemsetAsync(A.p, 0, sizeof(double) * N * N, s));
+    HIP_OK(hipMemsetAsync(gs.mg.cinfo.p, 0, sizeof(int), s));
+    hipLaunchKernelGGL(k_mg_coarse_dense, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, s,
+                       (const double*)gs.mg.off[qc].p, (const double*)gs.mg.diag[qc].p, ncl,
+                       gs.mg.n[qc], gs.mg.m[qc], l, c->cfg.periodic && c->npx == 1, A.p);
+    /* k_cr_inv reads column-major: it inverts A^T and writes the result column-major,
+     * which is A^-1 row-major -- the layout k_gemv applies */
+    if ((rc = cr_inverse_dev(s, N, A.p, gs.mg.cinv.p, gs.mg.cinfo.p))) return rc;
+    int info = 0;
+    if ((rc = d2h(c, &info, gs.mg.cinfo.p, sizeof(int)))) return rc;
+    if (info) {
+        set_error("block GS: singular coarsest T/S operator");
+        return IEMIC_EINVAL;
+    }
+    return 0;
+}
+
+/* larger coarsest levels and the subdomains' global coarsest problem: through the host */
+static int mg_coarse_host(iemic_ctx* c, int qc, int64_t ncl, int N)
+{
+    BlockGS& gs = c->gs;
+    const int l = c->l;
+    int rc;
+    std::vector<double> off(16 * ncl), dg(4 * ncl);
+    if ((rc = d2h(c, off.data(), gs.mg.off[qc].p, sizeof(double) * off.size()))) return rc;
+    if ((rc = d2h(c, dg.data(), gs.mg.diag[qc].p, sizeof(double) * dg.size()))) return rc;
+    std::vector<double> A((size_t)N * N, 0.0), X;
+    const int cn = gs.mg.n[qc], cm = gs.mg.m[qc];
+    for (int64_t t = 0; t < ncl; t++) {
+        int i, jl, k;
+        mg_decode(t, cn, l, i, jl, k);
+        for (int R = 0; R < 2; R++) {
+            const int64_t row = R * ncl + t;
+            A[row * N + R * ncl + t] += dg[(3 * R) * ncl + t];
+            A[row * N + (1 - R) * ncl + t] += dg[(1 + R) * ncl + t];
+            for (int qq = 0; qq < 8; qq++) {
+                const double v = off[(8 * R + qq) * ncl + t];
+                if (v == 0.0) continue;
+                int ii = i, jj = jl, kk = k;
+                const int dir = qq < 6 ? qq : qq - 2;
+                switch (dir) {
+                case 0: ii--; break;
+                case 1: ii++; break;
+                case 2: jj--; break;
+                case 3: jj++; break;
+                case 4: kk--; break;
+                default: kk++; break;
+                }
+                if (jj < 0 || jj >= cm || kk < 0 || kk >= l) continue;
+                if (ii < 0 || ii >= cn) {
+                    if (!(c->cfg.periodic && c->npx == 1)) continue;
+                    ii = (ii + cn) % cn;
+                }
+                const int64_t nb = ((int64_t)jj * cn + ii) * l + kk;
+                const int var = qq < 6 ? R : 1 - R;
+                A[row * N + var * ncl + nb] += v;
+            }
+        }
+    }
+    dense_inverse(A, N, X);
+    if ((rc = h2d(c, gs.mg.cinv.p, X.data(), sizeof(double) * X.size()))) return rc;
+    return mg_global_setup(c, off, dg);
+}
+
+/* levels, Galerkin operators, z-line factors and the coarsest inverse (once per Jacobian) */
+int ts_mg_setup(iemic_ctx* c, int sweeps)
+{
+    BlockGS& gs = c->gs;
+    int rc;
+    gs.mg.sweeps = sweeps;
+    if (gs.ts_mg <= 0) return 0;
+    if (c->l > 64) {             /* the z-line smoother runs one lane per level */
+        gs.ts_mg = 0;
+        return 0;
+    }
+    if (gs.mg.nlev == 0) {
+        if ((rc = mg_levels(c))) return rc;
+        if (gs.ts_mg == 0) return 0;
+    }
+    if ((rc = mg_operators(c))) return rc;
+    const int qc = gs.mg.nlev - 1;
+    const int64_t ncl = (int64_t)gs.mg.n[qc] * gs.mg.m[qc] * c->l;
+    const int N = (int)(2 * ncl);
+    if (gs.mg.crd) return mg_coarse_cr(c, qc, ncl, N);
+    if (N <= 192 && c->nranks <= 1) return mg_coarse_dev(c, qc, ncl, N);
+    return mg_coarse_host(c, qc, ncl, N);
+}
+
+/* refresh the level-0 iterate's halo columns (phase x, owned rows) and halo rows (phase
+ * y, whole rows with their halo columns) -- the subdomains coupled in the T/S smoother */
+static int mg_halo(iemic_ctx* c, const TsLev& V)
+{
+    if (!V.vis && !V.visi) return 0;
+    const int64_t W = V.n + 2 * V.hi, L = V.l;
+    const int w = c->nb[0], e = c->nb[1], so = c->nb[2], no = c->nb[3];
+    std::vector<Msg> x, y;
+    for (double* z : {V.z, V.z + V.cstr}) {
+        if (V.visi) {
+            auto col = [&](int64_t i) { return Seg{z, (V.hj * W + V.hi + i) * L, V.mb, L, W * L}; };
+            if (w >= 0) x.push_back({true, w, col(0)});
+            if (e >= 0) x.push_back({false, e, col(V.n)});
+            if (e >= 0) x.push_back({true, e, col(V.n - 1)});
+            if (w >= 0) x.push_back({false, w, col(-1)});
+        }
+        if (V.vis) {
+            auto row = [&](int64_t jl) { return Seg{z, (V.hj + jl) * W * L, 1, W * L, W * L}; };
+            if (so >= 0) y.push_back({true, so, row(0)});
+            if (no >= 0) y.push_back({false, no, row(V.mb)});
+            if (no >= 0) y.push_back({true, no, row(V.mb - 1)});
+            if (so >= 0) y.push_back({false, so, row(-1)});
+        }
+    }
+    int rc = run_msgs(c, x);
+    if (rc) return rc;
+    return run_msgs(c, y);
+}
+
+/* the bands' level 0 (mg_hr): the iterate's 2 rows next to each neighbour band, and with b
+ * its right-hand side's edge row -- for the halo-row line solves */
+static int mg_halo2(iemic_ctx* c, const TsLev& V, bool with_b)
+{
+    const int64_t RW = (int64_t)V.n * V.l;
+    const int so = c->nb[2], no = c->nb[3];
+    std::vector<Msg> y;
+    for (double* z : {V.z, V.z + V.cstr}) {
+        auto rows = [&](int jl) { return Seg{z, (V.hj + jl) * RW, 1, 2 * RW, 2 * RW}; };
+        if (so >= 0) y.push_back({true, so, rows(0)});
+        if (no >= 0) y.push_back({false, no, rows(V.mb)});
+        if (no >= 0) y.push_back({true, no, rows(V.mb - 2)});
+        if (so >= 0) y.push_back({false, so, rows(-2)});
+    }
+    if (with_b)
+        for (double* b : {V.b, V.b + V.cstr}) {
+            auto row = [&](int jl) { return Seg{b, (V.hj + jl) * RW, 1, RW, RW}; };
+            if (so >= 0) y.push_back({true, so, row(0)});
+            if (no >= 0) y.push_back({false, no, row(V.mb)});
+            if (no >= 0) y.push_back({true, no, row(V.mb - 1)});
+            if (so >= 0) y.push_back({false, so, row(-1)});
+        }
+    return run_msgs(c, y);
+}
+
+/* one colour launch of the z-line smoother (C: first post-smoothing sweep, zout: final;
+ * hr: the halo rows' lines too, mg_column) */
+static int mg_zl(iemic_ctx* c, const TsLev& V, int colour, const TsLev* C, double* zout, int hr = 0)
+{
+    hipStream_t s = c->stream;
+    const int P = mg_lanes(V.l);
+    const unsigned g = (unsigned)((mg_columns_of(V, colour, hr) * P + 63) / 64);
+    if (!g) return 0;
+    const TsLev Cv = C ? *C : V;
+    const int corr = C ? 1 : 0;
+    with_lanes(P, [&](auto p) {
+        hipLaunchKernelGGL(k_mg_zl<LANES_OF(p)>, dim3(g), dim3(64), 0, s, V, colour, Cv, corr, zout, hr);
+    });
+    return 0;
+}
+
+/* the coarsest level: z = A^-1 b (dense), or the bands' global coarsest problem */
+static int mg_coarsest(iemic_ctx* c, int q)
+{
+    BlockGS& gs = c->gs;
+    hipStream_t s = c->stream;
+    int rc;
+    const int N = 2 * gs.mg.n[q] * gs.mg.m[q] * c->l;
+    if (gs.mg.glob) {
+        /* gather the bands' right-hand sides, own rows of X b */
+        const int64_t ncl = N / 2;
+        if ((rc = dev_zero(c, gs.mg.gvec.p, gs.mg.gN))) return rc;
+        hipLaunchKernelGGL(k_mg_gput, dim3(blocks_for(ncl)), dim3(256), 0, s, gs.mg.b[q].p, ncl,
+                           gs.mg.n[q], c->l, gs.mg.gGX, gs.mg.gI0, gs.mg.gJ0, gs.mg.gvec.p);
+        if ((rc = allreduce_sum(c, gs.mg.gvec.p, gs.mg.gN))) return rc;
+        hipLaunchKernelGGL(k_gemv, dim3((unsigned)((gs.mg.gN + 3) / 4)), dim3(256), 0, s, gs.mg.gX.p,
+                           gs.mg.gN, gs.mg.gN, gs.mg.gvec.p, gs.mg.gtmp.p);
+        hipLaunchKernelGGL(k_mg_gget, dim3(blocks_for(ncl)), dim3(256), 0, s, gs.mg.gtmp.p, ncl,
+                           gs.mg.n[q], c->l, gs.mg.gGX, gs.mg.gI0, gs.mg.gJ0, gs.mg.z[q].p);
+        return 0;
+    }
+    if (N <= 1024)
+        hipLaunchKernelGGL(k_gemv_w<16>, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, (const double*)gs.mg.cinv.p,
+                           N, (const double*)gs.mg.b[q].p, gs.mg.z[q].p);
+    else if (N <= 2048)
+        hipLaunchKernelGGL(k_gemv_w<32>, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, (const double*)gs.mg.cinv.p,
+                           N, (const double*)gs.mg.b[q].p, gs.mg.z[q].p);
+    else
+        hipLaunchKernelGGL(k_gemv, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, gs.mg.cinv.p, N, N,
+                           gs.mg.b[q].p, gs.mg.z[q].p);
+    return 0;
+}
+
+/* One V-cycle from level q.  first: the level's iterate started at 0 and its colour-0 lines
+ * were relaxed by the launch that formed its right-hand side (k_mg_entry / k_mg_rc).
+ * zout: the last level-0 sweep writes z(T, S) into the preconditioner output. */
+/* a coarse level visited by the fused launches (k_mg_dn / k_mg_up): two colours, one
+ * sweep, no halo on it or on its coarse level (one rank, or the bands' band-local levels) */
+static bool mg_fused(iemic_ctx* c, int q)
+{
+    BlockGS& gs = c->gs;
+    if (q < 1 || q + 1 >= gs.mg.nlev || std::max(1, gs.mg.sweeps) != 1 || !gs.mg.zu[q].p) return false;
+    const TsLev V = mg_view(c, q), C = mg_view(c, q + 1);
+    return mg_ncolour(V) == 2 && !V.hj && !V.hi && !V.vis && !V.visi && !C.hj && !C.hi && C.l == V.l;
+}
+/* level q as its coarse-correction source: the iterate after its post-smoothing */
+static TsLev mg_final(iemic_ctx* c, int q)
+{
+    TsLev V = mg_view(c, q);
+    if (mg_fused(c, q)) V.z = c->gs.mg.zu[q].p;
+    return V;
+}
+
+static int mg_vcycle(iemic_ctx* c, int q, bool first, double* zout)
+{
+    BlockGS& gs = c->gs;
+    hipStream_t s = c->stream;
+    int rc;
+    const TsLev V = mg_view(c, q);
+    const int nc = mg_ncolour(V), nu = std::max(1, gs.mg.sweeps);
+    if (first && !zout && mg_fused(c, q)) {
+        /* one launch down (colour 1 + restriction + the coarse colour 0), one launch up */
+        const int qc = gs.mg.nlev - 1;
+        const TsLev C = mg_view(c, q + 1);
+        const int P = mg_lanes(V.l);
+        const unsigned g = (unsigned)(C.n * C.mb);
+        const int relax = q + 1 < qc ? 1 : 0;
+        with_lanes(P, [&](auto p) {
+            hipLaunchKernelGGL(k_mg_dn<LANES_OF(p)>, dim3(g), dim3(10 * LANES_OF(p)), 0, s, V, C, relax);
+        });
+        if (q + 1 == qc) {
+            if ((rc = mg_coarsest(c, q + 1))) return rc;
+        } else if ((rc = mg_vcycle(c, q + 1, true, nullptr))) {
+            return rc;
+        }
+        const TsLev Cf = mg_final(c, q + 1);
+        double* zu = gs.mg.zu[q].p;
+        with_lanes(P, [&](auto p) {
+            hipLaunchKernelGGL(k_mg_up<LANES_OF(p)>, dim3(g), dim3(10 * LANES_OF(p)), 0, s, V, Cf, zu);
+        });
+        return 0;
+    }
+    /* the bands' level 0, one sweep of two colours from the entry kernel: one exchange of 2
+     * rows before each colour-1 launch, which relaxes the halo rows' colour-1 lines too
+     * (the neighbour's own lines, operation for operation), so that the restriction and the
+     * last colour-0 launch read them without another exchange (4 -> 2 batches per V-cycle) */
+    const bool hrel = q == 0 && gs.mg.hr && V.hj == 2 && nu == 1 && nc == 2 && first;
+    const int hr = hrel ? ((c->nb[2] >= 0 ? 1 : 0) | (c->nb[3] >= 0 ? 2 : 0)) : 0;
+    for (int sw = 0; sw < nu; sw++)
+        for (int h = (sw == 0 && first) ? 1 : 0; h < nc; h++) {
+            if ((rc = hrel ? mg_halo2(c, V, true) : mg_halo(c, V))) return rc;
+            if ((rc = mg_zl(c, V, h, nullptr, nullptr, hrel && h == 1 ? hr : 0))) return rc;
+        }
+    const int qc = gs.mg.nlev - 1;
+    const TsLev C = mg_view(c, q + 1);
+    if (!hrel && (rc = mg_halo(c, V))) return rc;
+    {
+        const int P = mg_lanes(V.l);
+        const int shortcut = (first && nu == 1 && nc == 2) ? 1 : 0;
+        const int relax = q + 1 < qc ? 1 : 0;
+        const unsigned g = (unsigned)(((int64_t)C.n * C.mb * P + 63) / 64);
+        with_lanes(P, [&](auto p) {
+            hipLaunchKernelGGL(k_mg_rc<LANES_OF(p)>, dim3(g), dim3(64), 0, s, V, C, shortcut, relax);
+        });
+    }
+    if (q + 1 == qc) {
+        if ((rc = mg_coarsest(c, q + 1))) return rc;
+    } else if ((rc = mg_vcycle(c, q + 1, true, nullptr))) {
+        return rc;
+    }
+    const TsLev Cf = mg_final(c, q + 1);
+    /* coarse correction: added where the first post-smoothing colours read it, or (level 0
+     * of a band group, whose lines also read the neighbour bands' rows) explicitly */
+    const bool corr = V.hj == 0 && V.hi == 0;
+    if (!corr)
+        hipLaunchKernelGGL(k_mg_prolong, dim3(blocks_for((int64_t)V.n * V.mb * V.l)), dim3(256), 0, s, V, Cf);
+    for (int sw = 0; sw < nu; sw++)
+        for (int h = nc - 1; h >= 0; h--) {
+            if (hrel) {
+                if (h == 1 && (rc = mg_halo2(c, V, false))) return rc;
+            } else if ((rc = mg_halo(c, V))) {
+                return rc;
+            }
+            if ((rc = mg_zl(c, V, h, corr && sw == 0 ? &Cf : nullptr, sw + 1 == nu ? zout : nullptr,
+                            hrel && h == 1 ? hr : 0)))
+                return rc;
+        }
+    return 0;
+}
+
+/* The T/S block solve by ts_mg V-cycles: the right-hand side rr_TS - A_TS,D z_D from the
+ * planar dynamics iterate zd (k_mg_entry), then the V-cycles, the result into z(T, S) of the
+ * output z only when out (else later by ts_mg_out).  side: the V-cycles (which read and
+ * write only the multigrid's own buffers once the entry kernel has formed the right-hand
+ * side) run on the side stream, forked after the entry kernel; gs_apply joins before
+ * ts_mg_out. */
+int ts_mg_solve(iemic_ctx* c, const double* zd, double* z, bool out, bool side)
+{
+    BlockGS& gs = c->gs;
+    const Lay L = lay_of(c);
+    hipStream_t s = c->stream;
+    const TsLev V0 = mg_view(c, 0);
+    const unsigned ge = (unsigned)(((c->nx + MG_TI - 1) / MG_TI) * V0.mb);
+    with_lanes(mg_lanes(c->l), [&](auto p) {
+        hipLaunchKernelGGL(k_mg_entry<LANES_OF(p)>, dim3(ge), dim3(256), 0, s, gs.act.vp, gs.knP.p, gs.kmask.p,
+                           gs.rrP.p, zd, L, V0);
+    });
+    if (side) {
+        HIP_OK(hipEventRecord(c->ev_fork, s));
+        HIP_OK(hipStreamWaitEvent(c->side, c->ev_fork, 0));
+        c->stream = c->side;
+    }
+    int rc = 0;
+    for (int cyc = 0; cyc < gs.ts_mg && !rc; cyc++)
+        rc = mg_vcycle(c, 0, cyc == 0, out && cyc + 1 == gs.ts_mg ? z : nullptr);
+    if (side) {
+        c->stream = s;
+        if (rc) return rc;
+        HIP_OK(hipEventRecord(c->ev_join, c->side));
+    }
+    if (rc) return rc;
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+/* level-0 iterate -> z(T, S) of the preconditioner output (k_mg_out), after an early solve */
+int ts_mg_out(iemic_ctx* c, double* z)
+{
+    const TsLev V0 = mg_view(c, 0);
+    hipLaunchKernelGGL(k_mg_out, dim3(blocks_for((int64_t)V0.n * V0.mb * V0.l)), dim3(256), 0, c->stream, V0, z);
+    return 0;
+}
+
+}  // namespace iemic

@@ -54,7 +54,7 @@ set -e
 
 ab_bts_t() {
 # T/S right-hand side coefficients with the default (temporal) load policy
-sed -i 's/? 0.0 : __builtin_nontemporal_load(val + (int64_t)(B + s) \* nloc + lc);/? 0.0 : val[(int64_t)(B + s) * nloc + lc];/' csrc/prec_gs.hip
+sed -i 's/? 0.0 : __builtin_nontemporal_load(val + (int64_t)(B + s) \* nloc + lc);/? 0.0 : val[(int64_t)(B + s) * nloc + lc];/' csrc/gs_internal.h
 }
 
 ab_coeffuse() {
@@ -467,13 +467,13 @@ sed -i 's/acc\[q\] += __builtin_nontemporal_load(val + (int64_t)s \* nloc + lc) 
 
 ab_gemvw_t() {
 # coarse T/S inverse GEMV with the default (temporal) load policy
-sed -i 's/a\[u\] = c < N ? __builtin_nontemporal_load(A + c) : 0.0;/a[u] = c < N ? A[c] : 0.0;/' csrc/prec_gs.hip
+sed -i 's/a\[u\] = c < N ? __builtin_nontemporal_load(A + c) : 0.0;/a[u] = c < N ? A[c] : 0.0;/' csrc/ts_mg.hip
 }
 
 ab_mg_unfused() {
 # A/B: the coarse T/S levels by the unfused launches (k_mg_zl + k_mg_rc) instead of k_mg_dn / k_mg_up
-sed -i 's/if (q < 1 || q + 1 >= gs.mg_nlev/if (true || q < 1 || q + 1 >= gs.mg_nlev/' csrc/prec_gs.hip
-grep -q "if (true || q < 1" csrc/prec_gs.hip
+sed -i 's/if (q < 1 || q + 1 >= gs.mg.nlev/if (true || q < 1 || q + 1 >= gs.mg.nlev/' csrc/ts_mg.hip
+grep -q "if (true || q < 1" csrc/ts_mg.hip
 }
 
 ab_mg_wg64() {
@@ -757,12 +757,12 @@ PY
 
 ab_xh1() {
 # x halos on the first 1 intermediate T/S levels only
-sed -i "s/^constexpr int MG_XHALO_LEVELS = 99;/constexpr int MG_XHALO_LEVELS = 1;/" csrc/prec_gs.hip
+sed -i "s/^constexpr int MG_XHALO_LEVELS = 99;/constexpr int MG_XHALO_LEVELS = 1;/" csrc/ts_mg.hip
 }
 
 ab_xh2() {
 # x halos on the first 2 intermediate T/S levels only
-sed -i "s/^constexpr int MG_XHALO_LEVELS = 99;/constexpr int MG_XHALO_LEVELS = 2;/" csrc/prec_gs.hip
+sed -i "s/^constexpr int MG_XHALO_LEVELS = 99;/constexpr int MG_XHALO_LEVELS = 2;/" csrc/ts_mg.hip
 }
 
 v=${1:?variant}

@@ -5,6 +5,8 @@ are compiled with -ffp-contract=off and restate the reference arithmetic); the s
 intcond residual entry (SRES=0) is a parallel reduction, rtol 1e-13; SpMV sums in a
 different order than the CSR oracle, rtol 1e-13 in the max norm relative to |J||x|.
 """
+import dataclasses
+
 import numpy as np
 import pytest
 
@@ -136,6 +138,27 @@ def test_block_gs_apply_matches_cpu(oracle_lib, Ocean, name):
     r = cf.synthetic_vector(c, seed=3)
     z = oc.applyPrecon(r)
     zc = P.apply(r)
+    assert np.all(np.isfinite(z))
+    assert np.max(np.abs(z - zc)) <= 1e-8 * np.max(np.abs(zc))
+
+
+def test_block_gs_apply_odd_n_matches_cpu(oracle_lib, Ocean):
+    """The generic two-colour T/S sweeps (k_gs_bts, k_gs_ts_half): plain sweeps on a grid that
+    is neither colour-compactable (odd n) nor periodic -- natl8 without its last longitude
+    (7 x 8 x 4) -- == the CPU twin."""
+    c = dataclasses.replace(cf.preset("natl8", mixing=0), n=7)
+    L0 = np.delete(golden_landm("natl8"), 8, axis=2)
+    oc = Ocean(c, landm=L0, solver_params={"Preconditioner": 2, "TS sweeps": 3, "Dyn iterations": 1,
+                                           "TS multigrid cycles": 0})
+    L = mask_fix(oracle_lib, c, L0)
+    o = oracle_lib.Oracle(c.ref_dict(), L, c.par_list())
+    x = cf.synthetic_state(c, L, amp_ts=1e-3)
+    oc.setState(x)
+    oc.computeJacobian()
+    oc.buildPreconditioner(force=True)
+    ov, _ = o.jacobian(x)
+    r = cf.synthetic_vector(c, seed=3)
+    z, zc = oc.applyPrecon(r), oracle_lib.BlockGS(o, ov, 3).apply(r)
     assert np.all(np.isfinite(z))
     assert np.max(np.abs(z - zc)) <= 1e-8 * np.max(np.abs(zc))
 
@@ -286,6 +309,31 @@ def test_ts_multigrid(oracle_lib, Ocean, name):
             assert np.max(np.abs(z - zl)) <= 1e-9 * np.max(np.abs(zl))
             assert np.array_equal(oc.applyPrecon(r1), oc.applyPrecon(r1))   # deterministic
     assert its[1] <= its[0] + 2, its
+
+
+@pytest.mark.parametrize("name", ["gateway16"])
+def test_ts_multigrid_two_sweeps(oracle_lib, Ocean, name):
+    """Two smoothing sweeps per multigrid level: every coarse level is visited by the unfused
+    launches (restriction, z-line colours, coarse correction) instead of k_mg_dn / k_mg_up.
+    gateway16 has an intermediate level (16x16 -> 8x8 -> 4x4).  The CPU twin has no such
+    variant: FGMRES with it converges to 1e-8 on the oracle's Jacobian, and the apply is linear
+    and deterministic, as test_ts_multigrid asks of one sweep."""
+    c, oc, o, L = make(Ocean, oracle_lib, name,
+                       solver_params={"Preconditioner": 2, "FGMRES iterations": 500,
+                                      "FGMRES tolerance": 1e-8, "Multigrid sweeps": 2})
+    x = cf.synthetic_state(c, L, amp_ts=1e-3)
+    oc.setState(x)
+    oc.computeJacobian()
+    ov, _ = o.jacobian(x)
+    b = o.spmv(ov, cf.synthetic_vector(c, seed=5))
+    sol = oc.solve(b)
+    res = np.linalg.norm(b - o.spmv(ov, sol)) / np.linalg.norm(b)
+    assert oc.last_solve.converged == 1 and res <= 1e-7, res
+    r1, r2 = cf.synthetic_vector(c, seed=3), cf.synthetic_vector(c, seed=4)
+    z = oc.applyPrecon(2.5 * r1 + r2)
+    zl = 2.5 * oc.applyPrecon(r1) + oc.applyPrecon(r2)
+    assert np.max(np.abs(z - zl)) <= 1e-9 * np.max(np.abs(zl))
+    assert np.array_equal(oc.applyPrecon(r1), oc.applyPrecon(r1))
 
 
 @pytest.mark.parametrize("name,prec", [("test6x6x4", 1), ("test6x6x4", 2), ("natl8", 2), ("2dmoc", 2),
