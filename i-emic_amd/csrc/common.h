@@ -316,7 +316,8 @@ struct Krylov {
     int mc = 0;
     int64_t nc = 0;
     DevBuf<double> Vc, rf, t, bp;
-    int zclean = 0;                  /* Z is zero on the identity rows of the current set-up */
+    int zclean = 0;                  /* leading columns of Z that are zero on the identity  */
+                                     /* rows of the current set-up                        */
 };
 
 constexpr int RED_BLOCKS = 1024;     /* partial-sum blocks of the reductions            */

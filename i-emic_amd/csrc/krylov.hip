@@ -1063,11 +1063,13 @@ int fgmres(iemic_ctx* c, const double* b, double* x, const iemic_krylov* opt, ie
     rc = ensure_krylov(c, m, NC);
     if (rc) return rc;
     /* the staged applies (gs_apply_c after an update pass) leave the identity rows of the
-     * preconditioned vectors Z alone: zero them once per set-up (kr.zclean), the other
-     * solvers may have left values there */
-    if (cmp && !c->kr.zclean) {
-        if ((rc = dev_zero(c, c->kr.Z.p, (int64_t)m * NE))) return rc;
-        c->kr.zclean = 1;
+     * preconditioned vectors Z alone: zero them once per set-up, the other solvers may have
+     * left values there.  kr.zclean counts the leading columns already zeroed: a solve with a
+     * larger m than the one that cleaned zeroes the columns in between */
+    if (cmp && c->kr.zclean < m) {
+        const int z0 = c->kr.zclean;
+        if ((rc = dev_zero(c, c->kr.Z.p + (int64_t)z0 * NE, (int64_t)(m - z0) * NE))) return rc;
+        c->kr.zclean = m;
     } else if (!cmp) {
         c->kr.zclean = 0;
     }

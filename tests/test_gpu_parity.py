@@ -166,7 +166,7 @@ def test_block_gs_apply_odd_n_matches_cpu(oracle_lib, Ocean):
 @pytest.mark.parametrize("name", ["natl8", "gateway16", "global4", "global2"])
 def test_block_gs_default_apply_matches_cpu(oracle_lib, Ocean, name):
     """The default block GS (4 damped defect-correction passes on the dynamics block, the
-    first two with the Schur solve, one T/S aggregation-multigrid V-cycle with z-line
+    first and the last with the Schur solve, one T/S aggregation-multigrid V-cycle with z-line
     smoothing, Mixing = 1) == its CPU twin
     (prec_oracle.c: band-LU Schur, block-Thomas z-lines)."""
     c, oc, o, L = make(Ocean, oracle_lib, name, mixing=1, solver_params={"Preconditioner": 2})
@@ -414,11 +414,6 @@ def test_nan_state_fails_cleanly(oracle_lib, Ocean):
     info = oc.newtonStep()
     assert info.solve.converged == 1 and info.solve.iters == ref.solve.iters
     assert info.norm_f1 == ref.norm_f1
-
-
-def _land_rows(c, L):
-    Li = L[1:-1, 1:-1, 1:-1].reshape(-1)
-    return np.repeat((Li != 0).astype(float), 6)
 
 
 @pytest.mark.parametrize("name,prec", [("test6x6x4", 2), ("natl8", 2), ("gateway16", 2),
