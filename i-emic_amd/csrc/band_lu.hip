@@ -44,7 +44,9 @@ __global__ void __launch_bounds__(1024) k_band_lu(double* __restrict__ ab, int n
         /* load the panel */
         for (int e = tid; e < nprow * NBP; e += nthr) {
             const int r = e / NBP, t = e % NBP;
-            P[r * PS + t] = (t < nbk && r <= t + bl) ? A(k0 + r, k0 + t) : 0.0;
+            /* columns right of row r's band (t - r > bl + bu, a band narrower than the panel)
+             * are not stored: zero, not the neighbouring rows' entries */
+            P[r * PS + t] = (t < nbk && r <= t + bl && t - r <= bl + bu) ? A(k0 + r, k0 + t) : 0.0;
         }
         __syncthreads();
         /* factorise the panel: wavefront 0 finds the pivot and interchanges the panel
@@ -101,7 +103,7 @@ __global__ void __launch_bounds__(1024) k_band_lu(double* __restrict__ ab, int n
         for (int e = tid; e < (NBP + bl) * NBP; e += nthr) {
             const int r = e / NBP, t = e % NBP;
             const bool in = r < nprow && t < nbk;
-            if (in && r <= t) A(k0 + r, k0 + t) = P[r * PS + t];
+            if (in && r <= t && t - r <= bl + bu) A(k0 + r, k0 + t) = P[r * PS + t];
             Lp[e] = (in && r > t) ? P[r * PS + t] : 0.0;
         }
         /* A12 (the panel rows right of the panel) and the rows below the panel that were

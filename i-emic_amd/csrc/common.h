@@ -123,6 +123,7 @@ struct CrPack {                      /* set-up copy: P[dst + c rc + rr] = s A[r0
 };
 struct CrStep {                      /* one apply launch                                  */
     int nwg = 0, rc = 16;            /* workgroups, rows per chunk                        */
+    int nl = 1;                      /* levels the step spans (1 or 2)                    */
     CrCls cls{};
     DevBuf<CrWg> wg;
     DevBuf<double> P;
@@ -156,6 +157,7 @@ int cr_factor_blocks(iemic_ctx* c, SchurCR& cr);
 int cr_check(iemic_ctx* c, SchurCR& cr);
 int cr_solve(iemic_ctx* c, const SchurCR& cr, const double* b, double* x, hipStream_t s, double* xT = nullptr);
 int cr_inverse_dev(hipStream_t s, int m, const double* src, double* dst, int* info);
+int cr_inverse(hipStream_t s, int m, int count, const double* src, int s0, int sstep, double* dst, int* info);
 
 /* T/S aggregation multigrid of the block GS (ts_mg.hip; BlockGS::mg, which no other unit
  * names): 2x2 horizontal aggregates, full depth, band-local; level q has n[q] x m[q] x l cells

@@ -906,6 +906,7 @@ static int cr_build_steps(iemic_ctx* c, SchurCR& cr)
             }
             /* down steps top-first in plan order; up steps applied bottom-first (reverse) */
             CrStep& st = dir == 0 ? cr.down[ip] : cr.up[plan.size() - 1 - ip];
+            st.nl = P.nl;
             int rc;
             if ((rc = cr_pack_step(c, cr, outs, st))) return rc;
         }
@@ -1043,8 +1044,8 @@ int cr_init(iemic_ctx* c, SchurCR& cr, int n, int m, int periodic, int tail_max)
     return cr_build_steps(c, cr);
 }
 
-static int cr_inverse(hipStream_t s, int m, int count, const double* src, int s0, int sstep, double* dst,
-                      int* info)
+/* the inverses of src blocks s0 + k sstep (k < count) into dst blocks k, one workgroup each */
+int cr_inverse(hipStream_t s, int m, int count, const double* src, int s0, int sstep, double* dst, int* info)
 {
     if (count <= 0) return 0;
 #define CR_INV(TR, RA, RB)                                                                           \
@@ -1170,6 +1171,11 @@ static void cr_step(const SchurCR& cr, const CrStep& st, const double* b, double
 int cr_solve(iemic_ctx* c, const SchurCR& cr, const double* b, double* x, hipStream_t s, double* xT)
 {
     (void)c;
+    if (cr.tM > CR_TAIL_MAX) {             /* k_cr_tail holds b and a row in arrays of that size */
+        set_error("Schur cyclic reduction: a dense tail of " + std::to_string(cr.tM) + " unknowns (more than " +
+                  std::to_string(CR_TAIL_MAX) + ") has no apply kernel");
+        return IEMIC_EINVAL;
+    }
     auto bvec = [&](int l) { return l == 0 ? b : cr.bv.p + cr.v_off[l]; };
     auto xvec = [&](int l) { return l == 0 ? x : cr.xv.p + cr.v_off[l]; };
     const int le = cr.tM ? cr.lt : cr.nlev;

@@ -1,0 +1,53 @@
+/*
+ * test_hooks.h -- entry points that drive the dense solvers of the preconditioner on their
+ * own (schur_cr.hip, band_lu.hip) for tests/test_gpu_dense.py.  They are exported from the
+ * device library but are NOT part of its public ABI (include/iemic.h, IEMIC_ABI_VERSION):
+ * tests/dense_hooks.py binds them.  All pointers are host pointers; every hook runs on the
+ * context's stream, owns its device buffers and returns the usual IEMIC_* codes.
+ */
+#ifndef IEMIC_TEST_HOOKS_H
+#define IEMIC_TEST_HOOKS_H
+
+#include "../../include/iemic.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define IEMIC_TEST_PLAN_LEN 128
+
+/* Block cyclic reduction of the n m x n m block tridiagonal system
+ *     L_i x_{i-1} + D_i x_i + R_i x_{i+1} = b_i      (periodic: indices mod n)
+ * D, L, R: n m x m column-major blocks each (cr_factor_blocks); D == NULL: the level-0 blocks
+ * come from the 9-point rows S9 (n m x 9) and col_of_ij (m x n) through cr_factor.
+ * nsolve right-hand sides b (nsolve x n m) are solved one after another on the same SchurCR
+ * into x, and into xT (transposed order, may be NULL).  *info: the device flag cr_check reads;
+ * cr_check's error is returned.  plan (IEMIC_TEST_PLAN_LEN ints): nlev, lt, tM, ncomp,
+ * nsteps, then for each down step and then each up step rc, nwg, cls.ncls, levels spanned. */
+int iemic_test_cr_solve(iemic_ctx* ctx, int n, int m, int periodic, int tail_max, const double* D,
+                        const double* L, const double* R, const double* S9, const int* col_of_ij,
+                        int nsolve, const double* b, double* x, double* xT, int* info, int* plan);
+
+/* One SchurCR factorised with the blocks (D1, L1, R1) and solved for b, then factorised again
+ * with (D2, L2, R2) and solved for b into x: what every Newton step does. */
+int iemic_test_cr_refactor(iemic_ctx* ctx, int n, int m, int periodic, int tail_max, const double* D1,
+                           const double* L1, const double* R1, const double* D2, const double* L2,
+                           const double* R2, const double* b, double* x);
+
+/* The batched Gauss-Jordan inverse as the levels call it: A holds nsrc m x m column-major
+ * blocks, block s0 + k sstep is inverted into X block k (k < count).  *info: the device flag. */
+int iemic_test_cr_inverse(iemic_ctx* ctx, int m, int count, int s0, int sstep, int nsrc, const double* A,
+                          double* X, int* info);
+
+/* band_lu_inverse with cols = 0 .. N-1: ab (N x (2 bl + bu + 1), gbtrf layout by rows) comes
+ * back factorised, piv (N) and X (N x N row-major; untouched when *info != 0) are written,
+ * *stage_o reports the branch of k_band_lu.  Shapes whose LDS need exceeds the device's are
+ * refused with IEMIC_EINVAL before any launch (*stage_o is still set). */
+int iemic_test_band_inverse(iemic_ctx* ctx, int N, int bl, int bu, double* ab, int* piv, double* X, int* info,
+                            int* stage_o);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif

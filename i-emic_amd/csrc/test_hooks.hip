@@ -1,0 +1,185 @@
+/*
+ * test_hooks.hip -- the dense solvers of the preconditioner driven on their own
+ * (test_hooks.h).  No kernels here: every hook stages host data, calls the production
+ * entry points of schur_cr.hip / band_lu.hip on the context's stream and copies back.
+ */
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "common.h"
+#include "test_hooks.h"
+
+using namespace iemic;
+
+namespace {
+
+/* LDS of one workgroup on gfx950 */
+constexpr size_t LDS_MAX = 160 * 1024;
+
+int bad(const char* what)
+{
+    set_error(std::string("test hook: ") + what);
+    return IEMIC_EINVAL;
+}
+
+void cr_plan(const SchurCR& cr, int* plan)
+{
+    std::fill(plan, plan + IEMIC_TEST_PLAN_LEN, 0);
+    plan[0] = cr.nlev;
+    plan[1] = cr.lt;
+    plan[2] = cr.tM;
+    plan[3] = cr.ncomp;
+    plan[4] = (int)cr.down.size();
+    int k = 5;
+    for (const auto* v : {&cr.down, &cr.up})
+        for (const CrStep& st : *v) {
+            if (k + 4 > IEMIC_TEST_PLAN_LEN) return;
+            plan[k++] = st.rc;
+            plan[k++] = st.nwg;
+            plan[k++] = st.cls.ncls;
+            plan[k++] = st.nl;
+        }
+}
+
+int cr_load_blocks(iemic_ctx* c, SchurCR& cr, const double* D, const double* L, const double* R)
+{
+    const size_t nb = (size_t)cr.n * cr.m * cr.m;
+    int rc;
+    if ((rc = h2d(c, cr.dlr.p, D, sizeof(double) * nb))) return rc;
+    if ((rc = h2d(c, cr.dlr.p + nb, L, sizeof(double) * nb))) return rc;
+    return h2d(c, cr.dlr.p + 2 * nb, R, sizeof(double) * nb);
+}
+
+/* one solve; x (and xT) are filled with NaN bit patterns first, so an entry the solve does
+ * not write cannot pass for a value left by the solve before */
+int cr_solve_one(iemic_ctx* c, const SchurCR& cr, DevBuf<double>& bd, DevBuf<double>& xd, DevBuf<double>& xtd,
+                 const double* b, double* x, double* xT)
+{
+    const size_t nm = (size_t)cr.n * cr.m;
+    int rc;
+    if ((rc = h2d(c, bd.p, b, sizeof(double) * nm))) return rc;
+    HIP_OK(hipMemsetAsync(xd.p, 0xff, sizeof(double) * nm, c->stream));
+    if (xT) HIP_OK(hipMemsetAsync(xtd.p, 0xff, sizeof(double) * nm, c->stream));
+    if ((rc = cr_solve(c, cr, bd.p, xd.p, c->stream, xT ? xtd.p : nullptr))) return rc;
+    if ((rc = d2h(c, x, xd.p, sizeof(double) * nm))) return rc;
+    if (xT && (rc = d2h(c, xT, xtd.p, sizeof(double) * nm))) return rc;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int iemic_test_cr_solve(iemic_ctx* c, int n, int m, int periodic, int tail_max, const double* D,
+                                   const double* L, const double* R, const double* S9, const int* col_of_ij,
+                                   int nsolve, const double* b, double* x, double* xT, int* info, int* plan)
+{
+    if (!c || !info || !plan) return bad("null argument");
+    if (c->nranks != 1) return bad("a single-rank context is needed");
+    if (n < 1 || m < 1 || nsolve < 0 || (int64_t)n * m > (1 << 24)) return bad("cyclic reduction shape out of range");
+    if (D ? (!L || !R) : (!S9 || !col_of_ij)) return bad("neither blocks nor 9-point rows");
+    if (nsolve && (!b || !x)) return bad("null right-hand side or solution");
+    *info = 0;
+    int rc;
+    SchurCR cr;
+    if ((rc = cr_init(c, cr, n, m, periodic ? 1 : 0, tail_max))) return rc;
+    cr_plan(cr, plan);
+    const size_t nm = (size_t)n * m;
+    if (D) {
+        if ((rc = cr_load_blocks(c, cr, D, L, R))) return rc;
+        if ((rc = cr_factor_blocks(c, cr))) return rc;
+    } else {
+        DevBuf<double> s9;
+        DevBuf<int> col;
+        if (s9.alloc(nm * 9) || col.alloc(nm)) return IEMIC_ENOMEM;
+        if ((rc = h2d(c, s9.p, S9, sizeof(double) * nm * 9))) return rc;
+        if ((rc = h2d(c, col.p, col_of_ij, sizeof(int) * nm))) return rc;
+        if ((rc = cr_factor(c, cr, s9.p, col.p))) return rc;
+        DEV_SYNC(c);
+    }
+    if ((rc = d2h(c, info, cr.info.p, sizeof(int)))) return rc;
+    if ((rc = cr_check(c, cr))) return rc;
+    DevBuf<double> bd, xd, xtd;
+    if (bd.alloc(nm) || xd.alloc(nm) || (xT && xtd.alloc(nm))) return IEMIC_ENOMEM;
+    for (int k = 0; k < nsolve; k++)
+        if ((rc = cr_solve_one(c, cr, bd, xd, xtd, b + k * nm, x + k * nm, xT ? xT + k * nm : nullptr))) return rc;
+    return 0;
+}
+
+extern "C" int iemic_test_cr_refactor(iemic_ctx* c, int n, int m, int periodic, int tail_max, const double* D1,
+                                      const double* L1, const double* R1, const double* D2, const double* L2,
+                                      const double* R2, const double* b, double* x)
+{
+    if (!c || !D1 || !L1 || !R1 || !D2 || !L2 || !R2 || !b || !x) return bad("null argument");
+    if (c->nranks != 1) return bad("a single-rank context is needed");
+    if (n < 1 || m < 1 || (int64_t)n * m > (1 << 24)) return bad("cyclic reduction shape out of range");
+    int rc;
+    SchurCR cr;
+    if ((rc = cr_init(c, cr, n, m, periodic ? 1 : 0, tail_max))) return rc;
+    const size_t nm = (size_t)n * m;
+    DevBuf<double> bd, xd, xtd;
+    if (bd.alloc(nm) || xd.alloc(nm)) return IEMIC_ENOMEM;
+    for (int pass = 0; pass < 2; pass++) {
+        if ((rc = cr_load_blocks(c, cr, pass ? D2 : D1, pass ? L2 : L1, pass ? R2 : R1))) return rc;
+        if ((rc = cr_factor_blocks(c, cr))) return rc;
+        if ((rc = cr_check(c, cr))) return rc;
+        if ((rc = cr_solve_one(c, cr, bd, xd, xtd, b, x, nullptr))) return rc;
+    }
+    return 0;
+}
+
+extern "C" int iemic_test_cr_inverse(iemic_ctx* c, int m, int count, int s0, int sstep, int nsrc, const double* A,
+                                     double* X, int* info)
+{
+    if (!c || !A || !X || !info) return bad("null argument");
+    if (m < 1 || count < 1 || nsrc < 1 || s0 < 0 || sstep < 1 || (int64_t)s0 + (int64_t)(count - 1) * sstep >= nsrc ||
+        count > 4096 || nsrc > 65536)
+        return bad("Gauss-Jordan batch out of range");
+    if (m > 192) {                           /* before any allocation: cr_inverse's own refusal */
+        return cr_inverse(c->stream, m, count, nullptr, s0, sstep, nullptr, nullptr);
+    }
+    const size_t mm = (size_t)m * m;
+    DevBuf<double> ad, xd;
+    DevBuf<int> id;
+    if (ad.alloc(nsrc * mm) || xd.alloc(count * mm) || id.alloc(1)) return IEMIC_ENOMEM;
+    int rc;
+    if ((rc = h2d(c, ad.p, A, sizeof(double) * nsrc * mm))) return rc;
+    HIP_OK(hipMemsetAsync(xd.p, 0xff, sizeof(double) * count * mm, c->stream));
+    HIP_OK(hipMemsetAsync(id.p, 0, sizeof(int), c->stream));
+    if ((rc = cr_inverse(c->stream, m, count, ad.p, s0, sstep, xd.p, id.p))) return rc;
+    if ((rc = d2h(c, X, xd.p, sizeof(double) * count * mm))) return rc;
+    return d2h(c, info, id.p, sizeof(int));
+}
+
+extern "C" int iemic_test_band_inverse(iemic_ctx* c, int N, int bl, int bu, double* ab, int* piv, double* X,
+                                       int* info, int* stage_o)
+{
+    if (!c || !ab || !piv || !X || !info || !stage_o) return bad("null argument");
+    if (N < 1 || bl < 0 || bu < 0 || N > 4096 || bl > 4096 || bu > 4096) return bad("band shape out of range");
+    /* the two LDS sizes as band_lu_inverse computes them */
+    const int NBP = BAND_NBP;
+    const size_t lb = sizeof(double) * ((size_t)(NBP + bl) * (NBP + 1) + (size_t)2 * NBP * (bl + bu));
+    const int so = lb <= 150 * 1024 ? 1 : 0;
+    const size_t lbu = so ? lb : lb - sizeof(double) * (size_t)NBP * (bl + bu);
+    const int ring = std::max(bl + NBP + 1, bl + bu + 1);
+    const size_t li = (size_t)(ring + 2 * NBP) * 16 * sizeof(double);
+    *stage_o = so;
+    if (lbu > LDS_MAX || li > LDS_MAX) return bad("band too wide for the LDS of the band kernels");
+    const int W = 2 * bl + bu + 1;
+    const size_t npan = (size_t)(N + NBP - 1) / NBP;
+    DevBuf<double> abd, xd, lpan;
+    DevBuf<int> pd, id, cd;
+    if (abd.alloc((size_t)N * W) || xd.alloc((size_t)N * N) || lpan.alloc(npan * (NBP + bl) * NBP) || pd.alloc(N) ||
+        id.alloc(1) || cd.alloc(N))
+        return IEMIC_ENOMEM;
+    std::vector<int> cols(N);
+    for (int q = 0; q < N; q++) cols[q] = q;
+    int rc;
+    if ((rc = h2d(c, cd.p, cols.data(), sizeof(int) * N))) return rc;
+    if ((rc = h2d(c, abd.p, ab, sizeof(double) * N * W))) return rc;
+    if ((rc = h2d(c, xd.p, X, sizeof(double) * N * N))) return rc;      /* the caller's prefill */
+    HIP_OK(hipMemsetAsync(pd.p, 0xff, sizeof(int) * N, c->stream));
+    if ((rc = band_lu_inverse(c, abd.p, N, bl, bu, pd.p, id.p, lpan.p, cd.p, xd.p, info))) return rc;
+    if ((rc = d2h(c, ab, abd.p, sizeof(double) * N * W))) return rc;
+    if ((rc = d2h(c, piv, pd.p, sizeof(int) * N))) return rc;
+    return d2h(c, X, xd.p, sizeof(double) * N * N);
+}

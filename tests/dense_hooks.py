@@ -1,0 +1,107 @@
+"""ctypes binding of the device library's test hooks (i-emic_amd/csrc/test_hooks.h): the
+block cyclic reduction, the batched Gauss-Jordan inverse and the band LU of the
+preconditioner, each driven on its own.  Not part of the public ABI (include/iemic.h)."""
+import ctypes as C
+
+import numpy as np
+
+from iemic import _lib
+
+PLAN_LEN = 128
+EINVAL = -22
+_PD, _PI = C.POINTER(C.c_double), C.POINTER(C.c_int)
+_bound = None
+
+
+def hooks():
+    global _bound
+    if _bound is None:
+        L = _lib.lib()
+        vp, i = C.c_void_p, C.c_int
+        L.iemic_test_cr_solve.restype = i
+        L.iemic_test_cr_solve.argtypes = [vp, i, i, i, i, _PD, _PD, _PD, _PD, _PI, i, _PD, _PD, _PD, _PI, _PI]
+        L.iemic_test_cr_refactor.restype = i
+        L.iemic_test_cr_refactor.argtypes = [vp, i, i, i, i] + [_PD] * 8
+        L.iemic_test_cr_inverse.restype = i
+        L.iemic_test_cr_inverse.argtypes = [vp, i, i, i, i, i, _PD, _PD, _PI]
+        L.iemic_test_band_inverse.restype = i
+        L.iemic_test_band_inverse.argtypes = [vp, i, i, i, _PD, _PI, _PD, _PI, _PI]
+        _bound = L
+    return _bound
+
+
+def last_error():
+    msg = _lib.lib().iemic_last_error()
+    return msg.decode() if msg else ""
+
+
+def _d(a):
+    return None if a is None else a.ctypes.data_as(_PD)
+
+
+def _colmajor(B):
+    """(n, m, m) blocks [i][row][col] -> the device's column-major blocks, flat"""
+    return np.ascontiguousarray(np.transpose(np.asarray(B, dtype=np.float64), (0, 2, 1))).reshape(-1)
+
+
+class Plan:
+    """the hook's plan array: level counts and, per apply step, (rc, nwg, ncls, levels)"""
+
+    def __init__(self, p):
+        self.nlev, self.lt, self.tM, self.ncomp, self.nsteps = (int(v) for v in p[:5])
+        q = [tuple(int(v) for v in p[5 + 4 * k: 9 + 4 * k]) for k in range(2 * self.nsteps)]
+        self.down, self.up = q[:self.nsteps], q[self.nsteps:]
+
+    def __repr__(self):
+        return (f"Plan(nlev={self.nlev}, lt={self.lt}, tM={self.tM}, ncomp={self.ncomp}, "
+                f"down={self.down}, up={self.up})")
+
+
+def cr_solve(h, n, m, periodic, tail_max, b, D=None, L=None, R=None, S9=None, col_of_ij=None, want_xT=False):
+    """-> (rc, x (nsolve, n m), xT or None, info, Plan).  b: (nsolve, n m) or None (plan only)."""
+    nm = n * m
+    nsolve = 0 if b is None else np.asarray(b).reshape(-1, nm).shape[0]
+    bb = None if b is None else np.ascontiguousarray(b, dtype=np.float64).reshape(-1)
+    x = np.full(max(nsolve, 1) * nm, np.nan)
+    xT = np.full(max(nsolve, 1) * nm, np.nan) if want_xT else None
+    info = C.c_int(-1)
+    plan = np.zeros(PLAN_LEN, dtype=np.int32)
+    blocks = [None if B is None else _colmajor(B) for B in (D, L, R)]
+    s9 = None if S9 is None else np.ascontiguousarray(S9, dtype=np.float64).reshape(-1)
+    col = None if col_of_ij is None else np.ascontiguousarray(col_of_ij, dtype=np.int32).reshape(-1)
+    rc = hooks().iemic_test_cr_solve(h, n, m, int(periodic), int(tail_max), _d(blocks[0]), _d(blocks[1]),
+                                     _d(blocks[2]), _d(s9), None if col is None else col.ctypes.data_as(_PI),
+                                     nsolve, _d(bb), _d(x), _d(xT), C.byref(info), plan.ctypes.data_as(_PI))
+    return (rc, x.reshape(max(nsolve, 1), nm)[:nsolve], None if xT is None else xT.reshape(-1, nm)[:nsolve],
+            info.value, Plan(plan))
+
+
+def cr_refactor(h, n, m, periodic, tail_max, first, second, b):
+    """factor `first` = (D, L, R), solve b; factor `second` on the same SchurCR, solve b -> (rc, x)"""
+    a = [_colmajor(B) for B in first] + [_colmajor(B) for B in second]
+    bb = np.ascontiguousarray(b, dtype=np.float64).reshape(-1)
+    x = np.full(n * m, np.nan)
+    rc = hooks().iemic_test_cr_refactor(h, n, m, int(periodic), int(tail_max), *[_d(v) for v in a], _d(bb), _d(x))
+    return rc, x
+
+
+def cr_inverse(h, A, s0, sstep, count):
+    """A: (nsrc, m, m) -> (rc, X (count, m, m), info): X[k] = inverse of A[s0 + k sstep]"""
+    A = np.asarray(A, dtype=np.float64)
+    nsrc, m = A.shape[0], A.shape[1]
+    a = _colmajor(A)
+    X = np.full(count * m * m, np.nan)
+    info = C.c_int(-1)
+    rc = hooks().iemic_test_cr_inverse(h, m, count, s0, sstep, nsrc, _d(a), _d(X), C.byref(info))
+    return rc, np.transpose(X.reshape(count, m, m), (0, 2, 1)), info.value
+
+
+def band_inverse(h, N, bl, bu, ab, prefill=np.nan):
+    """ab: (N, 2 bl + bu + 1) rows -> (rc, ab factored, piv, X (N, N), info, stage_o)"""
+    ab = np.array(ab, dtype=np.float64)
+    piv = np.full(max(N, 1), -1, dtype=np.int32)
+    X = np.full((max(N, 1), max(N, 1)), prefill, dtype=np.float64)
+    info, so = C.c_int(-1), C.c_int(-1)
+    rc = hooks().iemic_test_band_inverse(h, N, bl, bu, _d(ab), piv.ctypes.data_as(_PI), _d(X), C.byref(info),
+                                         C.byref(so))
+    return rc, ab, piv, X, info.value, so.value
