@@ -1,7 +1,7 @@
 /*
  * active_set.hip -- the compressed active-cell set of the block Gauss-Seidel set-up and the
  * coefficient streams packed from the Jacobian (BlockGS::act): what FGMRES's compressed
- * basis, the compressed SpMV and the dynamics defect (krylov.hip) read.
+ * basis, the compressed SpMV and the dynamics defect (krylov.hip, spmv.hip) read.
  */
 #include <algorithm>
 #include <vector>
@@ -34,7 +34,7 @@ __global__ void k_dyn_pack(const double* __restrict__ val, const int* __restrict
     dvb[t] = h < nact ? val[s * nloc + act[h]] : 0.0;
 }
 
-/* the compressed SpMV's stream (krylov.hip k_spmv7c): the active cells of tile pos (a0 ..
+/* the compressed SpMV's stream (spmv.hip k_spmv7c): the active cells of tile pos (a0 ..
  * a0 + na - 1) hold one contiguous run spc[104 a0 ..), slot s of active cell a at
  * 104 a0 + s na + (a - a0) */
 __global__ void k_spmv_pack(const double* __restrict__ val, const int* __restrict__ act,

@@ -204,7 +204,7 @@ int band_lu_inverse(iemic_ctx* c, double* ab, int N, int bl, int bu, int* piv, i
                     const int* cols, double* X, int* info);
 
 /* The compressed active-cell set and the coefficient streams packed from the Jacobian
- * (active_set.hip; BlockGS::act).  This is the part of the block GS that krylov.hip and
+ * (active_set.hip; BlockGS::act).  This is the part of the block GS that krylov.hip, spmv.hip and
  * assembly.hip may read; beside it they read only BlockGS::ready, kind, known, rrP, dyn_iters
  * and dyn_mr. */
 struct ActiveSet {
@@ -216,7 +216,7 @@ struct ActiveSet {
     DevBuf<uint8_t> actf;            /* per owned cell: 1 active (k_cell_active)           */
     int64_t nact = 0;
     std::vector<uint8_t> act_h;      /* the per-cell flags the list was built from        */
-    /* the compressed SpMV (krylov.hip k_spmv7c): the active cells' 104 coefficients blocked
+    /* the compressed SpMV (spmv.hip k_spmv7c): the active cells' 104 coefficients blocked
      * per tile (k_spmv_pack: no coefficient line holds a land cell or another tile's), and
      * the grid tiles that hold an active cell (8 ints each: tile, first | last active lane
      * << 8, first active cell, active cells, 64-bit active-lane mask, 0, 0) */
@@ -515,7 +515,7 @@ int compute_forcing(iemic_ctx* c);
  * and the salinity correction times gamma, on the host */
 int surface_fluxes(iemic_ctx* c, const double* x_dev, double* out9, double* scorr);
 int intcond_correction(iemic_ctx* c, const double* x_dev);
-/* krylov.hip */
+/* spmv.hip, krylov.hip, idrs.hip */
 /* y = J x on the owned rows; x (ext layout) gets its halo rows exchanged first */
 int spmv(iemic_ctx* c, double* x, double* y, hipStream_t s);
 int spmv_kernel(iemic_ctx* c, const double* x, double* y);

@@ -1,0 +1,44 @@
+/*
+ * krylov_internal.h -- what the ocean's Krylov units share (krylov.hip, idrs.hip): the launch
+ * grid of their element-wise kernels, the small numeric guards, and the helpers of krylov.hip
+ * that IDR(s) calls.  Included by nothing else.
+ */
+#ifndef IEMIC_KRYLOV_INTERNAL_H
+#define IEMIC_KRYLOV_INTERNAL_H
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+
+#include "common.h"
+
+namespace iemic {
+
+inline unsigned grid_for(int64_t N)
+{
+    int64_t b = (N + 255) / 256;
+    return (unsigned)std::min<int64_t>(b, 2048);
+}
+
+/* sqrt of a squared norm that rounding may have driven below zero; NaN stays NaN */
+inline double sqrt0(double v) { return v > 0.0 ? std::sqrt(v) : (v == v ? 0.0 : v); }
+
+/* krylov.hip */
+/* a NaN/Inf reaching the Hessenberg column would pass for a breakdown (res = 0): stop loudly */
+int nonfinite();
+double ms_since(std::chrono::steady_clock::time_point t0);
+/* dot products of nvec vectors V_i (stride ldv) with w, and (ea != null) ea . eb as
+ * out[nvec], in one launch pair and one host synchronisation */
+/* V, w, ea, eb point at the first owned row; length nlrows; sums over the ranks */
+int mdot_host(iemic_ctx* c, const double* V, int64_t ldv, int nvec, const double* w, double* out,
+              const double* ea = nullptr, const double* eb = nullptr);
+/* the Krylov work space: Z (m x N) and w, r always; the full-length basis V ((m+1) x N) unless
+ * the basis is compressed, then Vc ((m+1) x nc) and the full-length t, b' */
+int ensure_krylov(iemic_ctx* c, int m, int64_t nc = 0);
+/* coefficients -> device through the pinned staging area (the previous use of the area
+ * has completed: every caller synchronised the stream since) */
+int upload_coeffs(iemic_ctx* c, const double* h, int n);
+
+}  // namespace iemic
+
+#endif

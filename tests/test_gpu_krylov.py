@@ -1,4 +1,4 @@
-"""The Krylov machinery of csrc/krylov.hip against independent computations.
+"""The Krylov machinery of csrc/krylov.hip, spmv.hip and idrs.hip against independent computations.
 
 1. FGMRES iterates: with a fixed linear preconditioner the k-th iterate is defined by
    (A, M, b) alone, so the device solver (DCGS2 or DGKS, full-length or compressed basis,
