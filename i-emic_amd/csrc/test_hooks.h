@@ -1,6 +1,7 @@
 /*
  * test_hooks.h -- entry points that drive the dense solvers of the preconditioner on their
- * own (schur_cr.hip, band_lu.hip) for tests/test_gpu_dense.py.  They are exported from the
+ * own (schur_cr.hip, band_lu.hip) for tests/test_gpu_dense.py, and the coupled model's
+ * preconditioner (coupled.hip) for tests/test_gpu_coupled_krylov.py.  They are exported from the
  * device library but are NOT part of its public ABI (include/iemic.h, IEMIC_ABI_VERSION):
  * tests/dense_hooks.py binds them.  All pointers are host pointers; every hook runs on the
  * context's stream, owns its device buffers and returns the usual IEMIC_* codes.
@@ -45,6 +46,16 @@ int iemic_test_cr_inverse(iemic_ctx* ctx, int m, int count, int s0, int sstep, i
  * refused with IEMIC_EINVAL before any launch (*stage_o is still set). */
 int iemic_test_band_inverse(iemic_ctx* ctx, int N, int bl, int bu, double* ab, int* piv, double* X, int* info,
                             int* stage_o);
+
+/* The coupled model's forward block Gauss-Seidel preconditioner (cpl_prec, coupled.hip) on
+ * host vectors [ocean (reference order) | atmosphere]: pack, z_o = M_o^-1 r_o,
+ * z_a = M_a^-1 (r_a - C_ao z_o), unpack; use_prec == 0: z = r.  The Jacobians must be current.
+ * The atmosphere's preconditioner is computed first when it is not current (prec_valid).
+ * The ocean's is computed, in its default kind, only when none was ever computed: a new ocean
+ * Jacobian does not mark it stale, so the caller rebuilds it, as iemic_coupled_solve does
+ * before every solve.  The device copy of z starts as NaN bit patterns, so an entry that
+ * cpl_prec does not write comes back as NaN. */
+int iemic_test_coupled_prec(iemic_coupled* cm, const double* r_host, double* z_host, int use_prec);
 
 #ifdef __cplusplus
 }

@@ -1,13 +1,15 @@
 /*
- * test_hooks.hip -- the dense solvers of the preconditioner driven on their own
- * (test_hooks.h).  No kernels here: every hook stages host data, calls the production
- * entry points of schur_cr.hip / band_lu.hip on the context's stream and copies back.
+ * test_hooks.hip -- the dense solvers of the preconditioner and the coupled model's block
+ * Gauss-Seidel preconditioner driven on their own (test_hooks.h).  No kernels here: every
+ * hook stages host data, calls the production entry points of schur_cr.hip / band_lu.hip /
+ * coupled.hip on the context's stream and copies back.
  */
 #include <algorithm>
 #include <cstring>
 #include <vector>
 
 #include "common.h"
+#include "coupled_internal.h"
 #include "test_hooks.h"
 
 using namespace iemic;
@@ -182,4 +184,33 @@ extern "C" int iemic_test_band_inverse(iemic_ctx* c, int N, int bl, int bu, doub
     if ((rc = d2h(c, ab, abd.p, sizeof(double) * N * W))) return rc;
     if ((rc = d2h(c, piv, pd.p, sizeof(int) * N))) return rc;
     return d2h(c, X, xd.p, sizeof(double) * N * N);
+}
+
+extern "C" int iemic_test_coupled_prec(iemic_coupled* cm, const double* r_host, double* z_host, int use_prec)
+{
+    if (!cm || !r_host || !z_host) return bad("null argument");
+    iemic_ctx* oc = cm->oc;
+    iemic_atmos* a = cm->at;
+    if (hipSetDevice(oc->device) != hipSuccess) return IEMIC_EDEVICE;
+    if (!oc->jac_valid || !a->jac_valid) {
+        set_error("test hook: no Jacobian assembled");
+        return IEMIC_ESTATE;
+    }
+    StreamGuard guard{oc};
+    int rc;
+    if (use_prec) {
+        if (!oc->gs.ready && (rc = prec_compute(oc, nullptr))) return rc;
+        if (!a->prec_valid && (rc = atm_prec_compute(a))) return rc;
+    }
+    const int64_t NC = cm->NC;
+    std::vector<double> packed;
+    pack_host(cm, r_host, packed);
+    DevBuf<double> dr, dz;
+    if (dr.alloc(NC) || dz.alloc(NC)) return IEMIC_ENOMEM;
+    if ((rc = h2d(oc, dr.p, packed.data(), sizeof(double) * NC))) return rc;
+    HIP_OK(hipMemsetAsync(dz.p, 0xff, sizeof(double) * NC, oc->stream));
+    if ((rc = cpl_prec(cm, dr.p, dz.p, use_prec))) return rc;
+    if ((rc = d2h(oc, packed.data(), dz.p, sizeof(double) * NC))) return rc;
+    unpack_host(cm, packed, z_host);
+    return 0;
 }

@@ -26,8 +26,21 @@ def hooks():
         L.iemic_test_cr_inverse.argtypes = [vp, i, i, i, i, i, _PD, _PD, _PI]
         L.iemic_test_band_inverse.restype = i
         L.iemic_test_band_inverse.argtypes = [vp, i, i, i, _PD, _PI, _PD, _PI, _PI]
+        L.iemic_test_coupled_prec.restype = i
+        L.iemic_test_coupled_prec.argtypes = [vp, _PD, _PD, i]
         _bound = L
     return _bound
+
+
+def coupled_prec(cm, r, use_prec):
+    """cpl_prec of a iemic.coupled.CoupledModel on a host vector [ocean | atmosphere] -> z"""
+    r = np.ascontiguousarray(r, dtype=np.float64)
+    assert r.size == cm.N
+    z = np.full(cm.N, np.nan)
+    rc = hooks().iemic_test_coupled_prec(cm._h, _d(r), _d(z), int(use_prec))
+    if rc:
+        raise RuntimeError(f"iemic_test_coupled_prec: {rc} {last_error()}")
+    return z
 
 
 def last_error():

@@ -1,12 +1,15 @@
-"""The CPU reference GMRES (tests/krylov_ref.py) checked against itself: the GPU tests of
-tests/test_gpu_krylov.py compare the device FGMRES with it to 1e-12 (residual) and 1e-11
-(iterate), so its own rounding error must be far below that."""
+"""The CPU references of tests/krylov_ref.py checked against themselves.  The GPU tests of
+tests/test_gpu_krylov.py compare the device FGMRES with the reference GMRES to 1e-12
+(residual) and 1e-11 (iterate), so its own rounding error must be far below that; those of
+tests/test_gpu_idr.py and tests/test_gpu_coupled_krylov.py compare the device IDR(s) with
+idrs_ref at bounds taken from its float64-longdouble spread."""
 import numpy as np
 import pytest
 
 from helpers import golden_landm, mask_fix
 from iemic import config as cf
-from krylov_ref import csr_operator, fgmres_ref, krylov_lstsq_residual
+from krylov_ref import (IDR_CAP, IDR_KINDS, IDR_SEED_COUPLED, IDR_SEED_OCEAN, csr_operator, fgmres_ref,
+                        idr_kinds, idr_shadow_raw, idr_steps, idrs_ref, krylov_lstsq_residual)
 
 KS = (1, 2, 5, 8, 13, 21)
 
@@ -74,3 +77,134 @@ def test_reference_gmres_preconditioned(oracle_lib):
         assert abs(a.rho[k - 1] - p.rho[k - 1]) <= 1e-13 * p.rho[k - 1]
         xp = ML(p.x_steps[k - 1])
         assert np.linalg.norm((a.x_steps[k - 1] - xp).astype(float)) <= 1e-13 * np.linalg.norm(xp.astype(float))
+
+
+# ---- the IDR(s) reference --------------------------------------------------------------------
+def dense_system(N, seed=3):
+    """a well conditioned dense matrix (4 I + noise), b and a shadow space"""
+    rng = np.random.default_rng(seed)
+    A = 4.0 * np.eye(N) + rng.standard_normal((N, N)) / np.sqrt(N)
+    return A, rng.standard_normal(N), rng.uniform(-1, 1, (N, 8))
+
+
+def test_idr_shadow_raw_matches_python_integers():
+    """idr_shadow_raw (numpy uint64, wrapping) against the same splitmix64 in Python's
+    unbounded integers reduced mod 2^64, at rows that make the products wrap."""
+    M64 = (1 << 64) - 1
+
+    def one(row, q, seed):
+        z = (0x9E3779B97F4A7C15 * (row * 16 + q + 1) + seed) & M64
+        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M64
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M64
+        z ^= z >> 31
+        return 2.0 * ((z >> 11) / 9007199254740992.0) - 1.0
+
+    rows = np.array([0, 1, 5, 863, 24575, 273600, 2 ** 31 + 7])
+    for seed in (IDR_SEED_OCEAN, IDR_SEED_COUPLED):
+        raw = idr_shadow_raw(rows, 8, seed)
+        assert raw.shape == (len(rows), 8) and np.all(np.abs(raw) <= 1.0)
+        for a, row in enumerate(rows):
+            for q in range(8):
+                assert raw[a, q] == one(int(row), q, seed), (row, q, seed)
+    assert not np.array_equal(idr_shadow_raw(rows, 4, IDR_SEED_OCEAN), idr_shadow_raw(rows, 4, IDR_SEED_COUPLED))
+    # fewer shadow vectors: the leading columns of more
+    assert np.array_equal(idr_shadow_raw(rows, 4, IDR_SEED_OCEAN), idr_shadow_raw(rows, 8, IDR_SEED_OCEAN)[:, :4])
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.longdouble])
+@pytest.mark.parametrize("s", [1, 4])
+def test_idr_reference_dense(s, dtype):
+    """N = 12: the shadow space comes back orthonormal; every v of the cycles after the first
+    is orthogonal to P and the recursive r_k is b - A x_k, both to rounding (100 eps of the
+    magnitudes that were summed: for v the residual at the start of its cycle, whose P' r is
+    updated recursively, and |gamma_i| |g_i|); r_k is orthogonal to p_1 .. p_k inside a cycle; and IDR(s)
+    terminates: within N + N / s steps the residual is below 1e-10."""
+    N = 12
+    A, b, P = dense_system(N)
+    eps = float(np.finfo(dtype).eps)
+    steps = N + N // s
+    ref = idrs_ref(A.astype(dtype), None, b, P[:, :s], s, steps, dtype=dtype)
+    assert len(ref.x_steps) == len(ref.rho) == len(ref.rec) == len(ref.kind) == steps
+    Q = ref.P
+    assert np.max(np.abs((Q.T @ Q).astype(float) - np.eye(s))) <= 100 * eps
+    # in order: p_j lies in the span of the first j + 1 raw vectors
+    for j in range(s):
+        raw = P[:, :j + 1].astype(dtype)
+        c, *_ = np.linalg.lstsq(raw.astype(float), Q[:, j].astype(float), rcond=None)
+        assert np.linalg.norm((raw @ c.astype(dtype) - Q[:, j]).astype(float)) <= 1e-12
+    assert ref.kind[:s] == ["first"] * s and ref.kind[s] == "omega"
+    assert [k for k, *_ in ref.omega] == [q * (s + 1) for q in range(1, steps // (s + 1) + 1)]
+    assert len(ref.v) == sum(k == "gamma" for k in ref.kind) > 0
+    for step, v, scale in ref.v:
+        assert ref.kind[step - 1] == "gamma"
+        assert np.max(np.abs(Q.T @ v)) <= 100 * eps * scale, (step, float(np.max(np.abs(Q.T @ v))), float(scale))
+    bn = np.sqrt(b @ b)
+    Ad = A.astype(dtype)
+    for k in range(steps):
+        true = b.astype(dtype) - Ad @ ref.x_steps[k]
+        gap = np.linalg.norm((ref.r_steps[k] - true).astype(float))
+        assert gap <= 100 * eps * (bn + np.linalg.norm(A, 2) * np.linalg.norm(ref.x_steps[k].astype(float)))
+        kk = k % (s + 1)                      # column kk of a cycle: r is orthogonal to p_0 .. p_kk
+        if kk < s:
+            assert np.max(np.abs(Q[:, :kk + 1].T @ ref.r_steps[k])) <= 1e4 * eps * bn
+    print(f"s={s} {np.dtype(dtype).name}: rho", " ".join(f"{float(r):.1e}" for r in ref.rho))
+    assert min(ref.rho) < 1e-10
+    assert ref.rho[-1] < 1e-10
+
+
+def test_idr_reference_omega_rule():
+    """angle just under 1 makes the rule fire at every omega step, 1e-6 at none, and where it
+    fires omega is the minimal-residual value times angle / rho; preconditioned by a
+    diagonal M the iterates are M times those of the plain method on A M."""
+    A, b, P = dense_system(12)
+    hi = idrs_ref(A, None, b, P[:, :4], 4, 10, angle=0.999)
+    lo = idrs_ref(A, None, b, P[:, :4], 4, 10, angle=1e-6)
+    assert [f for _, _, f, _ in hi.omega] == [True, True]
+    assert [f for _, _, f, _ in lo.omega] == [False, False]
+    assert hi.omega[0][1] == lo.omega[0][1]            # the same first cycle, the same rho
+    assert abs(hi.omega[0][3] - lo.omega[0][3] * 0.999 / lo.omega[0][1]) <= 1e-14 * abs(hi.omega[0][3])
+    assert np.array_equal(hi.x_steps[3], lo.x_steps[3]) and not np.array_equal(hi.x_steps[4], lo.x_steps[4])
+    d = 1.0 + 0.5 * np.cos(np.arange(12))
+    a = idrs_ref(A, lambda v: v * d, b, P[:, :4], 4, 10)
+    p = idrs_ref(A * d[None, :], None, b, P[:, :4], 4, 10)
+    for k in range(10):
+        assert np.linalg.norm(a.x_steps[k] - d * p.x_steps[k]) <= 1e-12 * np.linalg.norm(a.x_steps[k])
+
+
+@pytest.mark.parametrize("name,s", [("test6x6x4", 1), ("test6x6x4", 4), ("test6x6x4", 8), ("gateway16", 4)])
+def test_idr_reference_spread_unpreconditioned(oracle_lib, name, s):
+    """The float64 and the longdouble IDR(s) reference on the oracle's ocean Jacobian, at the
+    steps the GPU test compares: their spread must leave the GPU test's bound (100 x, at least
+    1e-12) meaningful, i.e. stay below the 1e-8 cap at a step of every kind.  The angles are
+    the default and 0.999 (the rule fires at both omega steps).  With 1e-6 (it never fires) the
+    plain minimal-residual omega of this unpreconditioned, badly conditioned operator is
+    nearly zero (t is almost orthogonal to r) and the two references part by 2e-2 at the
+    second omega step of test6x6x4 with s = 4: that setting is compared with the block
+    Gauss-Seidel preconditioner only."""
+    c, L, o, ov, b = oracle_system(oracle_lib, name)
+    A64 = csr_operator(o.rowptr, o.col, ov, np.float64)
+    AL = csr_operator(o.rowptr, o.col, ov, np.longdouble)
+    P = idr_shadow_raw(np.arange(c.nrows), s, IDR_SEED_OCEAN)
+    ks = idr_steps(s)
+    for angle in (0.7, 0.999):
+        r64 = idrs_ref(A64, None, b, P, s, max(ks), angle, np.float64)
+        rL = idrs_ref(AL, None, b, P, s, max(ks), angle, np.longdouble)
+        kinds = set()
+        for k in ks:
+            x64, xL = r64.x_steps[k - 1], rL.x_steps[k - 1]
+            dx = float(np.linalg.norm((x64 - xL).astype(np.float64)) / np.linalg.norm(xL.astype(np.float64)))
+            drho = float(abs(r64.rho[k - 1] - rL.rho[k - 1]) / rL.rho[k - 1])
+            print(f"{name} s={s} angle={angle} k={k} {rL.kind[k - 1]}: rho {float(rL.rho[k - 1]):.6e} "
+                  f"spread x {dx:.2e} rho {drho:.2e}")
+            if dx <= IDR_CAP:
+                kinds |= idr_kinds(rL, [k])
+        assert IDR_KINDS <= kinds
+        assert [f for *_, f, _ in rL.omega] == [f for *_, f, _ in r64.omega]
+    if (name, s) == ("test6x6x4", 4):
+        # the reason angle 1e-6 is left to the preconditioned cases: over the cap here
+        k = 2 * s + 2
+        x64 = idrs_ref(A64, None, b, P, s, k, 1e-6, np.float64).x_steps[-1]
+        xL = idrs_ref(AL, None, b, P, s, k, 1e-6, np.longdouble).x_steps[-1]
+        dx = float(np.linalg.norm((x64 - xL).astype(np.float64)) / np.linalg.norm(xL.astype(np.float64)))
+        print(f"{name} s={s} angle=1e-6 k={k}: spread x {dx:.2e}")
+        assert dx > IDR_CAP
