@@ -72,8 +72,8 @@ static int act_tiles(iemic_ctx* c, const std::vector<uint8_t>& h, const std::vec
 {
     ActiveSet& as = c->gs.act;
     int rc;
-    const int nx = c->nx, tpr = (nx + 63) / 64;
-    const int64_t nrow = c->nloc / nx;
+    const int nx = c->sub.nx, tpr = (nx + 63) / 64;
+    const int64_t nrow = c->sub.nloc / nx;
     std::vector<int> tl, ap((size_t)as.nact, 0);
     for (int64_t row = 0; row < nrow; row++)
         for (int ti = 0; ti < tpr; ti++) {
@@ -108,27 +108,27 @@ int act_build(iemic_ctx* c, bool* changed)
     ActiveSet& as = gs.act;
     int rc;
     *changed = false;
-    if (as.actf.reserve(c->nloc)) return IEMIC_ENOMEM;
-    hipLaunchKernelGGL(k_cell_active, dim3(blocks_for(c->nloc)), dim3(256), 0, c->stream, gs.known.p, lay_of(c),
-                       as.actf.p);
-    std::vector<uint8_t> h((size_t)c->nloc);
+    if (as.actf.reserve(c->sub.nloc)) return IEMIC_ENOMEM;
+    hipLaunchKernelGGL(k_cell_active, dim3(blocks_for(c->sub.nloc)), dim3(256), 0, c->stream, gs.known.p,
+                       lay_of(c->sub), as.actf.p);
+    std::vector<uint8_t> h((size_t)c->sub.nloc);
     if ((rc = d2h(c, h.data(), as.actf.p, h.size()))) return rc;
     if (h == as.act_h) return 0;
     std::vector<int> list;
     list.reserve(h.size());
-    for (int64_t q = 0; q < c->nloc; q++)
+    for (int64_t q = 0; q < c->sub.nloc; q++)
         if (h[q]) list.push_back((int)q);
     as.nact = (int64_t)list.size();
     if (as.act.reserve(list.size() + 1)) return IEMIC_ENOMEM;
     if (!list.empty() && (rc = h2d(c, as.act.p, list.data(), sizeof(int) * list.size()))) return rc;
-    std::vector<int> cm((size_t)c->nloc, -1);
+    std::vector<int> cm((size_t)c->sub.nloc, -1);
     for (size_t q = 0; q < list.size(); q++) cm[list[q]] = (int)q;
     if (as.cmap.reserve(cm.size())) return IEMIC_ENOMEM;
     if ((rc = h2d(c, as.cmap.p, cm.data(), sizeof(int) * cm.size()))) return rc;
     as.ric = -1;
     if (c->rowintcon >= 0) {
-        const int64_t cell = c->rowintcon / NUN - c->own0;
-        if (cell >= 0 && cell < c->nloc && cm[cell] >= 0) as.ric = (int64_t)NUN * cm[cell] + c->rowintcon % NUN;
+        const int64_t cell = c->rowintcon / NUN - c->sub.own0;
+        if (cell >= 0 && cell < c->sub.nloc && cm[cell] >= 0) as.ric = (int64_t)NUN * cm[cell] + c->rowintcon % NUN;
     }
     if ((rc = act_tiles(c, h, cm))) return rc;
     as.act_h.swap(h);
@@ -142,14 +142,14 @@ int act_build(iemic_ctx* c, bool* changed)
 static int dyn_halo_coefs(iemic_ctx* c)
 {
     ActiveSet& as = c->gs.act;
-    const int64_t row = (int64_t)c->l * c->nx, nloc = c->nloc;
+    const int64_t row = (int64_t)c->l * c->sub.nx, nloc = c->sub.nloc;
     constexpr int NDS = 64;
     if (as.dvh.n < (size_t)(NDS * 2 * row)) {
         if (as.dvh.alloc((size_t)(NDS * 2 * row))) return IEMIC_ENOMEM;
         HIP_OK(hipMemsetAsync(as.dvh.p, 0, sizeof(double) * as.dvh.n, c->stream));
     }
     double* v = c->d_val.p;
-    const int so = c->nb[2], no = c->nb[3];
+    const int so = c->sub.nb[2], no = c->sub.nb[3];
     std::vector<Msg> y;
     if (so >= 0) y.push_back({true, so, Seg{v, 0, NDS, row, nloc}});
     if (no >= 0) y.push_back({false, no, Seg{as.dvh.p, row, NDS, row, 2 * row}});
@@ -167,7 +167,7 @@ static int act_pack_dvb(iemic_ctx* c)
     const int64_t nb = (as.nact + 63) / 64;
     if (as.dvb.reserve((size_t)(nb * 64 * 64))) return IEMIC_ENOMEM;
     hipLaunchKernelGGL(k_dyn_pack, dim3(blocks_for(nb * 64 * 64)), dim3(256), 0, c->stream, c->d_val.p,
-                       (const int*)as.act.p, as.nact, c->nloc, as.dvb.p, nb * 64 * 64);
+                       (const int*)as.act.p, as.nact, c->sub.nloc, as.dvb.p, nb * 64 * 64);
     HIP_OK(hipGetLastError());
     return 0;
 }
@@ -180,7 +180,7 @@ static int gs_pack_spc(iemic_ctx* c)
     if (as.nact <= 0 || !as.act.p) return 0;
     if (as.spc.reserve((size_t)(NSLOT * as.nact))) return IEMIC_ENOMEM;
     hipLaunchKernelGGL(k_spmv_pack, dim3(blocks_for(NSLOT * as.nact)), dim3(256), 0, c->stream, c->d_val.p,
-                       (const int*)as.act.p, (const int*)as.apos.p, (const int4*)as.atl.p, as.nact, c->nloc,
+                       (const int*)as.act.p, (const int*)as.apos.p, (const int4*)as.atl.p, as.nact, c->sub.nloc,
                        as.spc.p);
     HIP_OK(hipGetLastError());
     return 0;
@@ -192,7 +192,7 @@ int act_pack_streams(iemic_ctx* c)
 {
     ActiveSet& as = c->gs.act;
     int rc;
-    if (c->nranks > 1 && c->npx == 1 && (rc = dyn_halo_coefs(c))) return rc;
+    if (c->sub.nranks > 1 && c->sub.npx == 1 && (rc = dyn_halo_coefs(c))) return rc;
     if ((rc = act_pack_dvb(c))) return rc;
     if ((rc = gs_pack_spc(c))) return rc;
     as.vp = c->d_val.p;
@@ -217,8 +217,8 @@ int gs_refresh(iemic_ctx* c)
     as.coef_stale = 0;
     if (as.chk.reserve(1)) return IEMIC_ENOMEM;
     HIP_OK(hipMemsetAsync(as.chk.p, 0, sizeof(double), c->stream));
-    hipLaunchKernelGGL(k_known_diff, dim3((unsigned)((c->nloc + 255) / 256)), dim3(256), 0, c->stream,
-                       c->d_val.p, lay_of(c), (int64_t)c->rowintcon, gs.known.p, as.chk.p);
+    hipLaunchKernelGGL(k_known_diff, dim3((unsigned)((c->sub.nloc + 255) / 256)), dim3(256), 0, c->stream,
+                       c->d_val.p, lay_of(c->sub), (int64_t)c->rowintcon, gs.known.p, as.chk.p);
     int rc = allreduce_sum(c, as.chk.p, 1);
     if (rc) return rc;
     double nd = 0.0;

@@ -214,8 +214,8 @@ static int mix_control(iemic_ctx* c, const double* x_dev)
          * over the bands; only the two totals come to the host */
         const int nb = 256;
         double* part = c->d_red.p;
-        hipLaunchKernelGGL(k_ts_sq_partial, dim3(nb), dim3(256), 0, c->stream, x_dev, (int64_t)c->own0,
-                           (int64_t)c->nloc, part);
+        hipLaunchKernelGGL(k_ts_sq_partial, dim3(nb), dim3(256), 0, c->stream, x_dev, (int64_t)c->sub.own0,
+                           (int64_t)c->sub.nloc, part);
         hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(64), 0, c->stream, part, nb, part + 2 * nb);
         hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(64), 0, c->stream, part + nb, nb, part + 2 * nb + 1);
         int rc = allreduce_sum(c, part + 2 * nb, 2);
@@ -258,11 +258,11 @@ int assemble_jacobian(iemic_ctx* c, const double* x_dev)
         gs.act.coef_stale = 1;
     }
     Geo g = c->geo();
-    dim3 blk(128), grd((unsigned)((c->nloc + 127) / 128), NUN);
-    hipLaunchKernelGGL(k_jacobian, grd, blk, 0, c->stream, g, x_dev, c->d_val.p, c->nloc,
+    dim3 blk(128), grd((unsigned)((c->sub.nloc + 127) / 128), NUN);
+    hipLaunchKernelGGL(k_jacobian, grd, blk, 0, c->stream, g, x_dev, c->d_val.p, c->sub.nloc,
                        (int64_t)c->rowintcon);
-    hipLaunchKernelGGL(k_diagB, dim3((unsigned)((c->nloc + 255) / 256)), dim3(256), 0, c->stream,
-                       g, c->d_B.p, c->nloc, (int64_t)c->rowintcon);
+    hipLaunchKernelGGL(k_diagB, dim3((unsigned)((c->sub.nloc + 255) / 256)), dim3(256), 0, c->stream,
+                       g, c->d_B.p, c->sub.nloc, (int64_t)c->rowintcon);
     HIP_OK(hipGetLastError());
     c->jac_valid = 1;
     return 0;
@@ -273,15 +273,15 @@ int assemble_rhs(iemic_ctx* c, const double* x_dev, double* F_dev)
     int rc0 = mix_control(c, x_dev);
     if (rc0) return rc0;
     Geo g = c->geo();
-    dim3 blk(128), grd((unsigned)((c->nloc + 127) / 128), NUN);
-    hipLaunchKernelGGL(k_rhs, grd, blk, 0, c->stream, g, x_dev, c->d_frc.p, F_dev, c->nloc);
+    dim3 blk(128), grd((unsigned)((c->sub.nloc + 127) / 128), NUN);
+    hipLaunchKernelGGL(k_rhs, grd, blk, 0, c->stream, g, x_dev, c->d_frc.p, F_dev, c->sub.nloc);
     if (c->su.rowintcon_ref >= 0) {
         /* the integral condition couples every S unknown: owned partial dot, a sum over the
          * ranks, and the owning rank writes the entry */
         const int nb = 256;
-        const int64_t o = NUN * c->own0;
+        const int64_t o = NUN * c->sub.own0;
         hipLaunchKernelGGL(k_dot_partial, dim3(nb), dim3(256), 0, c->stream, c->d_intc.p + o,
-                           x_dev + o, c->nlrows, c->d_red.p);
+                           x_dev + o, c->sub.nlrows(), c->d_red.p);
         hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(64), 0, c->stream, c->d_red.p, nb,
                            c->d_red.p + nb);
         int rc = allreduce_sum(c, c->d_red.p + nb, 1);
@@ -302,8 +302,8 @@ int intcond_correction(iemic_ctx* c, const double* x_dev)
         return 0;
     }
     const int nb = 256;
-    const int64_t o = NUN * c->own0;
-    hipLaunchKernelGGL(k_dot_partial, dim3(nb), dim3(256), 0, c->stream, c->d_intc.p + o, x_dev + o, c->nlrows,
+    const int64_t o = NUN * c->sub.own0;
+    hipLaunchKernelGGL(k_dot_partial, dim3(nb), dim3(256), 0, c->stream, c->d_intc.p + o, x_dev + o, c->sub.nlrows(),
                        c->d_red.p);
     hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(64), 0, c->stream, c->d_red.p, nb, c->d_red.p + nb);
     int rc = allreduce_sum(c, c->d_red.p + nb, 1);
@@ -316,8 +316,8 @@ int compute_forcing(iemic_ctx* c)
     Geo g = c->geo();
     hipLaunchKernelGGL(k_qint, dim3(1), dim3(64), 0, c->stream, g, c->d_ftab.p, c->d_qcor.p,
                        c->cfg.tres == 0 ? 1 : 0, c->cfg.sres == 0 ? 1 : 0);
-    hipLaunchKernelGGL(k_forcing, dim3((unsigned)((c->nloc + 255) / 256)), dim3(256), 0,
-                       c->stream, g, c->d_ftab.p, c->d_qcor.p, c->d_frc.p, c->nloc);
+    hipLaunchKernelGGL(k_forcing, dim3((unsigned)((c->sub.nloc + 255) / 256)), dim3(256), 0,
+                       c->stream, g, c->d_ftab.p, c->d_qcor.p, c->d_frc.p, c->sub.nloc);
     HIP_OK(hipGetLastError());
     return 0;
 }
@@ -327,7 +327,7 @@ int compute_forcing(iemic_ctx* c)
  * salinity correction is the same sequential sum on every rank, whatever the decomposition */
 int surface_fluxes(iemic_ctx* c, const double* x_dev, double* out9, double* scorr)
 {
-    const int nm = c->n * c->m, mb = c->jb1 - c->jb0, ns = c->nx * mb;
+    const int nm = c->n * c->m, mb = c->sub.mb, ns = c->sub.nx * mb;
     DevBuf<double> d;
     if (d.alloc((size_t)NFLUX * nm + 1)) {
         set_error("surface_fluxes: out of device memory");

@@ -134,33 +134,33 @@ int upload_landm(iemic_ctx* c)
 int mask_fix(iemic_ctx* c)
 {
     const int n = c->n, m = c->m;
-    HIP_OK(hipMemsetAsync(c->d_tmp1.p, 0, sizeof(double) * c->nerows, c->stream));
+    HIP_OK(hipMemsetAsync(c->d_tmp1.p, 0, sizeof(double) * c->sub.nerows(), c->stream));
     const int pb = ROW_BEGIN[PP], pn = ROW_BEGIN[PP + 1] - ROW_BEGIN[PP];
-    std::vector<double> pv((size_t)pn * c->nloc);
+    std::vector<double> pv((size_t)pn * c->sub.nloc);
     DevBuf<double> dflag;
-    if (c->nranks > 1 && dflag.alloc(c->ncell)) return IEMIC_ENOMEM;
+    if (c->sub.nranks > 1 && dflag.alloc(c->ncell)) return IEMIC_ENOMEM;
     std::vector<double> flag;
     for (int cyc = 0; cyc < std::max(1, c->cfg.max_mask_fixes); cyc++) {
         int rc = assemble_jacobian(c, c->d_tmp1.p);
         if (rc) return rc;
-        if ((rc = d2h(c, pv.data(), c->d_val.p + (size_t)pb * c->nloc, sizeof(double) * pv.size())))
+        if ((rc = d2h(c, pv.data(), c->d_val.p + (size_t)pb * c->sub.nloc, sizeof(double) * pv.size())))
             return rc;
         flag.assign(c->ncell, 0.0);
-        for (int64_t lc = 0; lc < c->nloc; lc++) {
+        for (int64_t lc = 0; lc < c->sub.nloc; lc++) {
             int i, j, k;
             c->su.owned_ijk(lc, i, j, k);
             if (NUN * c->su.ref_cell(i, j, k) + PP == c->su.rowintcon_ref) continue;
             double sum = 0.0;
             int el = 0;
             for (int s = 0; s < pn; s++) {
-                double v = pv[(size_t)s * c->nloc + lc];
+                double v = pv[(size_t)s * c->sub.nloc + lc];
                 sum += v;
                 if (std::fabs(v) > 1e-10) el++;
             }
             if (sum == 1) continue;
             if (el <= 2) flag[c->su.ref_cell(i, j, k)] = 1.0;
         }
-        if (c->nranks > 1) {
+        if (c->sub.nranks > 1) {
             if ((rc = h2d(c, dflag.p, flag.data(), sizeof(double) * c->ncell))) return rc;
             if ((rc = allreduce_sum(c, dflag.p, (int)c->ncell))) return rc;
             if ((rc = d2h(c, flag.data(), dflag.p, sizeof(double) * c->ncell))) return rc;
@@ -290,33 +290,10 @@ static int create_impl(iemic_ctx** out, const iemic_grid* grid, const int* landm
     c->n = grid->n; c->m = grid->m; c->l = grid->l;
     c->ncell = (int64_t)c->n * c->m * c->l;
     c->nrows = NUN * c->ncell;
-    c->sub = sub;
-    c->rank = sub.rank;
-    c->nranks = sub.nranks;
-    c->npx = sub.npx;
-    c->npy = sub.npy;
-    c->px = sub.px;
-    c->py = sub.py;
-    c->ib0 = sub.ib0;
-    c->ib1 = sub.ib1;
-    c->jb0 = sub.jb0;
-    c->jb1 = sub.jb1;
-    for (int d = 0; d < 4; d++) c->nb[d] = sub.nb[d];
+    c->su.init(*grid, landm, sub);
     const int n = c->n, m = c->m, l = c->l;
     const size_t nl = (size_t)(n + 2) * (m + 2) * (l + 2);
-    {
-        const int s0[2] = {c->ib0, c->jb0}, s1[2] = {c->ib1, c->jb1};
-        c->su.init(*grid, landm, s0, s1, sub.npx > 1 ? 1 : 0);
-    }
-    c->nx = c->su.nx;
-    c->hx = c->su.hx;
-    c->xb = c->su.xb;
     c->su.vmix_init();
-    c->nloc = c->su.nloc;
-    c->nlrows = NUN * c->nloc;
-    c->next = c->su.next;
-    c->nerows = NUN * c->next;
-    c->own0 = c->su.own0();
     c->rowintcon = c->su.rowintcon;
     int rc = 0;
     if (a.group) local_group_join(c, a.group);
@@ -330,7 +307,7 @@ static int create_impl(iemic_ctx** out, const iemic_grid* grid, const int* landm
         delete c;
         return rc;
     }
-    const int64_t NE = c->nerows;
+    const int64_t NE = c->sub.nerows();
     rc |= c->d_landm.alloc(nl);
     rc |= c->d_ftab.alloc((size_t)3 * (m + 2) + (size_t)n * m);
     rc |= c->d_frc.alloc(NE);
@@ -340,7 +317,7 @@ static int create_impl(iemic_ctx** out, const iemic_grid* grid, const int* landm
     rc |= c->d_x.alloc(NE);
     rc |= c->d_F.alloc(NE);
     rc |= c->d_B.alloc(NE);
-    rc |= c->d_val.alloc((size_t)NSLOT * c->nloc);
+    rc |= c->d_val.alloc((size_t)NSLOT * c->sub.nloc);
     rc |= c->d_tmp1.alloc(NE);
     rc |= c->d_tmp2.alloc(NE);
     rc |= c->d_red.alloc(2048);
@@ -414,14 +391,14 @@ namespace {
 /* host reference-ordered global vector -> ext layout on the device (owned rows; halo 0) */
 int put_ref(iemic_ctx* c, const double* ref, double* dev)
 {
-    std::vector<double> e((size_t)c->nerows, 0.0);
+    std::vector<double> e((size_t)c->sub.nerows(), 0.0);
     c->su.ref_to_ext(ref, e.data());
     return h2d(c, dev, e.data(), sizeof(double) * e.size());
 }
 /* ext layout on the device -> owned rows of a host reference-ordered global vector */
 int get_ref(iemic_ctx* c, const double* dev, double* ref)
 {
-    std::vector<double> e((size_t)c->nerows);
+    std::vector<double> e((size_t)c->sub.nerows());
     int rc = d2h(c, e.data(), dev, sizeof(double) * e.size());
     if (rc) return rc;
     c->su.ext_to_ref(e.data(), ref);
@@ -522,18 +499,10 @@ extern "C" int iemic_landm(const iemic_ctx* c, int* out)
 extern "C" int iemic_layout(const iemic_ctx* c, int64_t* out)
 {
     if (!c || !out) return IEMIC_EINVAL;
-    out[0] = c->nerows;
-    out[1] = NUN * c->own0;
-    out[2] = c->nlrows;
-    out[3] = c->jb0;
-    out[4] = c->jb1;
-    out[5] = c->rank;
-    out[6] = c->nranks;
-    out[7] = c->ib0;
-    out[8] = c->ib1;
-    out[9] = c->npx;
-    out[10] = c->npy;
-    out[11] = c->hx;
+    const Sub& S = c->sub;
+    const int64_t v[12] = {S.nerows(), NUN * S.own0, S.nlrows(), S.jb0, S.jb1, S.rank,
+                           S.nranks,   S.ib0,        S.ib1,      S.npx, S.npy, S.hx};
+    std::copy(v, v + 12, out);
     return 0;
 }
 
@@ -608,8 +577,8 @@ extern "C" int iemic_set_state_dev(iemic_ctx* c, const double* x_dev)
 {
     CTX_CHECK(c);
     if (!x_dev) return IEMIC_EINVAL;
-    hipLaunchKernelGGL(k_ref_to_ext, dim3((unsigned)((c->nloc + 255) / 256)), dim3(256), 0, c->stream,
-                       x_dev, c->d_x.p, c->n, c->m, c->l, c->jb0, c->ib0, c->nx, c->nloc);
+    hipLaunchKernelGGL(k_ref_to_ext, dim3((unsigned)((c->sub.nloc + 255) / 256)), dim3(256), 0, c->stream,
+                       x_dev, c->d_x.p, c->n, c->m, c->l, c->sub.jb0, c->sub.ib0, c->sub.nx, c->sub.nloc);
     HIP_OK(hipGetLastError());
     c->jac_valid = 0;
     return 0;
@@ -636,13 +605,13 @@ int host_state(iemic_ctx* c, std::vector<double>& x)
 {
     int rc = halo_exchange(c, c->d_x.p, HALO);
     if (rc) return rc;
-    x.assign((size_t)c->nerows, 0.0);
+    x.assign((size_t)c->sub.nerows(), 0.0);
     return d2h(c, x.data(), c->d_x.p, sizeof(double) * x.size());
 }
 /* sum of a host array over the ranks */
 int host_sum(iemic_ctx* c, std::vector<double>& v)
 {
-    if (c->nranks <= 1) return 0;
+    if (c->sub.nranks <= 1) return 0;
     DevBuf<double> d;
     if (d.alloc(v.size())) return IEMIC_ENOMEM;
     int rc = h2d(c, d.p, v.data(), sizeof(double) * v.size());
@@ -657,7 +626,7 @@ extern "C" int iemic_allreduce_sum(iemic_ctx* c, double* buf, int64_t count)
 {
     CTX_CHECK(c);
     if (count < 0 || (count > 0 && !buf) || count > INT32_MAX) return IEMIC_EINVAL;
-    if (c->nranks <= 1 || count == 0) return 0;
+    if (c->sub.nranks <= 1 || count == 0) return 0;
     std::vector<double> v(buf, buf + count);
     int rc = host_sum(c, v);
     if (!rc) std::copy(v.begin(), v.end(), buf);
@@ -680,11 +649,11 @@ extern "C" int iemic_psim(iemic_ctx* c, double* psim_min, double* psim_max, doub
     const Geo g = su.geo(su.landm.data(), su.tab.data());
     const int n = c->n, m = c->m, l = c->l;
     std::vector<double> ps((size_t)(m + 1) * (l + 1), 0.0);
-    for (int j = c->jb0 + 1; j <= c->jb1 && j <= m; j++) {          /* 1-based, owned */
+    for (int j = c->sub.jb0 + 1; j <= c->sub.jb1 && j <= m; j++) {          /* 1-based, owned */
         const double cs = std::cos(su.yv[j]);
         for (int k = 1; k <= l; k++) {
             double sum = 0.0;
-            for (int i = c->ib0 + 1; i <= c->ib1; i++) sum += uv_arr(g, x.data(), VV, i, j, k);
+            for (int i = c->sub.ib0 + 1; i <= c->sub.ib1; i++) sum += uv_arr(g, x.data(), VV, i, j, k);
             const double vs = sum * su.dx;
             const double zk = host::fz(((double)k - 0.5) * su.dz + host::zmin, su.cfg.qz);
             if (zk * su.cfg.hdim < -500.0)
@@ -728,9 +697,9 @@ extern "C" int iemic_integral_checks(iemic_ctx* c, double* salt_advection, doubl
     std::vector<double> sums(2, 0.0);
     for (int k = 1; k <= l; k++) {
         const double h1 = 1.0 / (su.dfzT[k] * su.dfzW[k]), h2 = 1.0 / (su.dfzT[k] * su.dfzW[k - 1]);
-        for (int j = c->jb0 + 1; j <= c->jb1 && j <= m; j++) {
+        for (int j = c->sub.jb0 + 1; j <= c->sub.jb1 && j <= m; j++) {
             const double cay = std::cos(su.y[j]), c1 = std::cos(su.yv[j]), c2 = std::cos(su.yv[j - 1]);
-            for (int i = c->ib0 + 1; i <= c->ib1; i++) {
+            for (int i = c->sub.ib0 + 1; i <= c->sub.ib1; i++) {
                 if (LM(g, i, j, l) == OCEAN)
                     sums[0] += (u(i, j, k) + u(i, j - 1, k)) * (sa(i + 1, j, k) + sa(i, j, k)) / (4 * dx) -
                                (u(i - 1, j, k) + u(i - 1, j - 1, k)) * (sa(i, j, k) + sa(i - 1, j, k)) / (4 * dx) +
@@ -774,8 +743,8 @@ extern "C" int iemic_get_fluxes(iemic_ctx* c, const double* x, double* out, doub
     std::vector<double> all((size_t)NFLUX * nm);
     if ((rc = surface_fluxes(c, xd, all.data(), scorr))) return rc;
     for (int f = 0; f < NFLUX; f++)
-        for (int j = c->jb0; j < c->jb1; j++)
-            for (int i = c->ib0; i < c->ib1; i++) {
+        for (int j = c->sub.jb0; j < c->sub.jb1; j++)
+            for (int i = c->sub.ib0; i < c->sub.ib1; i++) {
                 const size_t q = f * nm + (size_t)j * c->n + i;
                 out[q] = all[q];
             }
@@ -909,7 +878,7 @@ extern "C" int iemic_export_csr(iemic_ctx* c, int64_t* rowptr, int* col, double*
         set_error("iemic_export_csr: no Jacobian assembled");
         return IEMIC_ESTATE;
     }
-    std::vector<double> v((size_t)NSLOT * c->nloc);
+    std::vector<double> v((size_t)NSLOT * c->sub.nloc);
     int rc = d2h(c, v.data(), c->d_val.p, sizeof(double) * v.size());
     if (rc) return rc;
     c->su.to_csr(v.data(), rowptr, col, val);
@@ -963,7 +932,7 @@ extern "C" int iemic_solve(iemic_ctx* c, const double* b, double* x, const iemic
     CTX_CHECK(c);
     if (!opt || !b || !x) return IEMIC_EINVAL;
     DevBuf<double> db, dx;
-    if (db.alloc(c->nerows) || dx.alloc(c->nerows)) return IEMIC_ENOMEM;
+    if (db.alloc(c->sub.nerows()) || dx.alloc(c->sub.nerows())) return IEMIC_ENOMEM;
     int rc = put_ref(c, b, db.p);
     if (rc) return rc;
     if ((rc = krylov_solve(c, db.p, dx.p, opt, info))) return rc;
@@ -994,7 +963,7 @@ extern "C" int iemic_newton_step(iemic_ctx* c, const iemic_krylov* opt, iemic_ne
     using clk = std::chrono::steady_clock;
     auto ms = [](clk::time_point a) { return std::chrono::duration<double, std::milli>(clk::now() - a).count(); };
     auto T0 = clk::now();
-    const int64_t o = NUN * c->own0, NL = c->nlrows;
+    const int64_t o = NUN * c->sub.own0, NL = c->sub.nlrows();
     const unsigned G = (unsigned)std::min<int64_t>((NL + 255) / 256, 2048);
     auto t = clk::now();
     int rc = halo_exchange(c, c->d_x.p, HALO);
@@ -1077,12 +1046,12 @@ extern "C" int iemic_vec_alloc(iemic_ctx* c, double** v)
     CTX_CHECK(c);
     if (!v) return IEMIC_EINVAL;
     *v = nullptr;
-    if (hipMalloc((void**)v, sizeof(double) * c->nerows) != hipSuccess) {
+    if (hipMalloc((void**)v, sizeof(double) * c->sub.nerows()) != hipSuccess) {
         *v = nullptr;
         set_error("iemic_vec_alloc: out of device memory");
         return IEMIC_ENOMEM;
     }
-    HIP_OK(hipMemsetAsync(*v, 0, sizeof(double) * c->nerows, c->stream));
+    HIP_OK(hipMemsetAsync(*v, 0, sizeof(double) * c->sub.nerows(), c->stream));
     return 0;
 }
 
@@ -1098,7 +1067,7 @@ extern "C" int iemic_vec_update(iemic_ctx* c, double a, const double* x, double 
 {
     CTX_CHECK(c);
     if (!x || !z) return IEMIC_EINVAL;
-    const int64_t o = NUN * c->own0, NL = c->nlrows;
+    const int64_t o = NUN * c->sub.own0, NL = c->sub.nlrows();
     const unsigned G = (unsigned)std::min<int64_t>((NL + 255) / 256, 2048);
     hipLaunchKernelGGL(k_vec_update, dim3(G), dim3(256), 0, c->stream, a, x + o, b, y ? y + o : nullptr, cz,
                        z + o, NL);
@@ -1117,7 +1086,7 @@ extern "C" int iemic_vec_norm_inf(iemic_ctx* c, const double* x, double* out)
 {
     CTX_CHECK(c);
     if (!x || !out) return IEMIC_EINVAL;
-    const int64_t o = NUN * c->own0, NL = c->nlrows;
+    const int64_t o = NUN * c->sub.own0, NL = c->sub.nlrows();
     const int nb = (int)std::min<int64_t>((NL + 255) / 256, RED_BLOCKS);
     hipLaunchKernelGGL(k_vec_absmax, dim3(nb), dim3(256), 0, c->stream, x + o, NL, c->d_part.p);
     HIP_OK(hipGetLastError());
@@ -1126,10 +1095,10 @@ extern "C" int iemic_vec_norm_inf(iemic_ctx* c, const double* x, double* out)
     if (rc) return rc;
     double mx = 0.0;
     for (double v : part) mx = (v > mx || v != v) ? v : mx;
-    if (c->nranks > 1) {
+    if (c->sub.nranks > 1) {
         /* max over the ranks: each rank's value in its own slot, summed */
-        std::vector<double> all((size_t)c->nranks, 0.0);
-        all[(size_t)c->rank] = mx;
+        std::vector<double> all((size_t)c->sub.nranks, 0.0);
+        all[(size_t)c->sub.rank] = mx;
         if ((rc = host_sum(c, all))) return rc;
         mx = 0.0;
         for (double v : all) mx = (v > mx || v != v) ? v : mx;
@@ -1157,13 +1126,13 @@ extern "C" int iemic_state_vec(iemic_ctx* c, double* v, int set)
 {
     CTX_CHECK(c);
     if (!v) return IEMIC_EINVAL;
-    const int64_t o = NUN * c->own0;
+    const int64_t o = NUN * c->sub.own0;
     if (set) {
-        HIP_OK(hipMemcpyAsync(c->d_x.p + o, v + o, sizeof(double) * c->nlrows, hipMemcpyDeviceToDevice,
+        HIP_OK(hipMemcpyAsync(c->d_x.p + o, v + o, sizeof(double) * c->sub.nlrows(), hipMemcpyDeviceToDevice,
                               c->stream));
         c->jac_valid = 0;
     } else {
-        HIP_OK(hipMemcpyAsync(v + o, c->d_x.p + o, sizeof(double) * c->nlrows, hipMemcpyDeviceToDevice,
+        HIP_OK(hipMemcpyAsync(v + o, c->d_x.p + o, sizeof(double) * c->sub.nlrows(), hipMemcpyDeviceToDevice,
                               c->stream));
     }
     return 0;
@@ -1177,9 +1146,9 @@ extern "C" int iemic_rhs_vec(iemic_ctx* c, double* F)
     int rc = halo_exchange(c, c->d_x.p, HALO);
     if (rc) return rc;
     if ((rc = assemble_rhs(c, c->d_x.p, c->d_F.p))) return rc;
-    const int64_t o = NUN * c->own0;
+    const int64_t o = NUN * c->sub.own0;
     if (F != c->d_F.p)
-        HIP_OK(hipMemcpyAsync(F + o, c->d_F.p + o, sizeof(double) * c->nlrows, hipMemcpyDeviceToDevice,
+        HIP_OK(hipMemcpyAsync(F + o, c->d_F.p + o, sizeof(double) * c->sub.nlrows(), hipMemcpyDeviceToDevice,
                               c->stream));
     return 0;
 }
@@ -1220,7 +1189,7 @@ extern "C" int iemic_time_prec(iemic_ctx* c, int nrep, double* ms_per_apply, dou
         return IEMIC_EDEVICE;
     }
     hipEvent_t e0 = ev.a, e1 = ev.b;
-    HIP_OK(hipMemsetAsync(c->d_tmp1.p, 0, sizeof(double) * c->nerows, c->stream));
+    HIP_OK(hipMemsetAsync(c->d_tmp1.p, 0, sizeof(double) * c->sub.nerows(), c->stream));
     int rc = prec_apply(c, c->d_tmp1.p, c->d_tmp2.p);   /* warm */
     if (rc) return rc;
     DEV_SYNC(c);

@@ -56,7 +56,7 @@ static int local_allreduce(iemic_ctx* c, double* dev, int count)
     int rc = d2h(c, h.data(), dev, sizeof(double) * count);
     if (rc) return rc;
     std::string err;
-    if (g->sum(c->rank, h.data(), h.data(), count, c->comm_timeout_s, err)) {
+    if (g->sum(c->sub.rank, h.data(), h.data(), count, c->comm_timeout_s, err)) {
         set_error(err);
         return err.find("did not arrive") != std::string::npos ? IEMIC_EDEVICE : IEMIC_EINVAL;
     }
@@ -67,7 +67,7 @@ static int group_barrier(iemic_ctx* c, LocalGroup* g, const char* what)
 {
     if (g->barrier(c->comm_timeout_s)) return 0;
     std::string err;
-    LocalGroup::timed_out(err, what, c->rank, c->comm_timeout_s);
+    LocalGroup::timed_out(err, what, c->sub.rank, c->comm_timeout_s);
     set_error(err);
     return IEMIC_EDEVICE;
 }
@@ -81,13 +81,13 @@ void local_group_free(void* g)
 void local_group_join(iemic_ctx* c, void* g)
 {
     c->group = g;
-    ((LocalGroup*)g)->attach(c->rank);
+    ((LocalGroup*)g)->attach(c->sub.rank);
 }
 void local_group_leave(iemic_ctx* c)
 {
     LocalGroup* g = (LocalGroup*)c->group;
     c->group = nullptr;
-    if (g && g->detach(c->rank)) delete g;
+    if (g && g->detach(c->sub.rank)) delete g;
 }
 
 int comm_unique_id(unsigned char* id128)
@@ -121,14 +121,14 @@ void comm_destroy(iemic_ctx* c)
  * its nranks) */
 int comm_size(const iemic_ctx* c, int* size, int* kind)
 {
-    if (c->nranks <= 1) {
+    if (c->sub.nranks <= 1) {
         *size = 1;
         *kind = 0;
     } else if (c->group) {
         *size = ((LocalGroup*)c->group)->P;
         *kind = 2;
     } else if (c->tp.send) {
-        *size = c->nranks;
+        *size = c->sub.nranks;
         *kind = 3;
     } else {
         int n = 0;
@@ -170,7 +170,7 @@ static int rccl_wait(iemic_ctx* c, const std::string& what, hipEvent_t e = nullp
         if (failed || dt > c->comm_timeout_s) {
             (void)ncclCommAbort(comm);
             c->comm = nullptr;
-            set_error(what + " on rank " + std::to_string(c->rank) + ": " +
+            set_error(what + " on rank " + std::to_string(c->sub.rank) + ": " +
                       (failed ? std::string("RCCL error ") + ncclGetErrorString(ae)
                               : "not complete after " + std::to_string(c->comm_timeout_s) +
                                     " s (a peer never posted the matching call)") +
@@ -200,7 +200,7 @@ static int rccl_live(iemic_ctx* c)
 
 int allreduce_sum(iemic_ctx* c, double* dev, int count)
 {
-    if (c->nranks <= 1 || count <= 0) return 0;
+    if (c->sub.nranks <= 1 || count <= 0) return 0;
     c->stat[3]++;
     if (c->group) return local_allreduce(c, dev, count);
     if (c->tp.send) return host_allreduce(c, dev, count);
@@ -287,7 +287,7 @@ static int run_local(iemic_ctx* c, const std::vector<Msg>& ops)
         std::vector<double> h(seg_count(op.s));
         HIP_OK(hipMemcpyAsync(h.data(), buf[q], sizeof(double) * h.size(), hipMemcpyDeviceToHost, c->stream));
         HIP_OK(hipStreamSynchronize(c->stream));
-        g->post(c->rank, op.peer, ksend[op.peer]++, std::move(h));
+        g->post(c->sub.rank, op.peer, ksend[op.peer]++, std::move(h));
     }
     if ((rc = group_barrier(c, g, "halo batch"))) return rc;
     bool ok = true;
@@ -295,7 +295,7 @@ static int run_local(iemic_ctx* c, const std::vector<Msg>& ops)
         const Msg& op = ops[q];
         if (op.send) continue;
         std::vector<double> h;
-        if (!(ok = g->take(op.peer, c->rank, krecv[op.peer]++, seg_count(op.s), h))) break;
+        if (!(ok = g->take(op.peer, c->sub.rank, krecv[op.peer]++, seg_count(op.s), h))) break;
         HIP_OK(hipMemcpyAsync(buf[q], h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, c->stream));
         HIP_OK(hipStreamSynchronize(c->stream));
     }
@@ -304,7 +304,7 @@ static int run_local(iemic_ctx* c, const std::vector<Msg>& ops)
     /* the second meeting also after an unmatched receive, so the peers are not left waiting */
     if ((rc = group_barrier(c, g, "halo batch"))) return rc;
     if (!ok) {
-        set_error("rank group: unmatched receive on rank " + std::to_string(c->rank));
+        set_error("rank group: unmatched receive on rank " + std::to_string(c->sub.rank));
         return IEMIC_EINVAL;
     }
     return 0;
@@ -403,7 +403,7 @@ static int run_rccl(iemic_ctx* c, const std::vector<Msg>& ops)
 
 int run_msgs(iemic_ctx* c, const std::vector<Msg>& ops)
 {
-    if (c->nranks <= 1 || ops.empty()) return 0;
+    if (c->sub.nranks <= 1 || ops.empty()) return 0;
     c->stat[0]++;
     for (const Msg& op : ops)
         if (op.send) {
@@ -427,7 +427,7 @@ void halo_plan_ext(const iemic_ctx* c, double* v, int width, int depth, std::vec
 
 int halo_exchange_w(iemic_ctx* c, double* v, int width, int depth)
 {
-    if (c->nranks <= 1) return 0;
+    if (c->sub.nranks <= 1) return 0;
     std::vector<Msg> x, y;
     halo_plan_ext(c, v, width, depth, x, y);
     int rc = run_msgs(c, x);
@@ -442,7 +442,7 @@ int halo_exchange_w(iemic_ctx* c, double* v, int width, int depth)
  * blocks at stride ps) -- same plan on every rank, so the pairing rule holds */
 int halo_exchange_planar(iemic_ctx* c, double* v, int nplanes, int64_t ps, int depth)
 {
-    if (c->nranks <= 1) return 0;
+    if (c->sub.nranks <= 1) return 0;
     std::vector<Msg> x0, y0, x, y;
     halo_plan_ext(c, v, 1, depth, x0, y0);
     const bool merge = c->group || c->tp.send;
@@ -470,8 +470,8 @@ int halo_exchange_planar(iemic_ctx* c, double* v, int nplanes, int64_t ps, int d
 
 int comm_verify_plans(iemic_ctx* c)
 {
-    if (c->nranks <= 1) return 0;
-    const int P = c->nranks;
+    if (c->sub.nranks <= 1) return 0;
+    const int P = c->sub.nranks;
     const int spec[4][2] = {{NUN, HALO}, {NUN, 1}, {1, 1}, {1, HALO}};   /* (width, depth) of the plans */
     /* per plan, per ordered pair (a -> b): message count and sum of (k + 1) * length over
      * the k-th message; the sender adds, the receiver subtracts: all zero when they pair */
@@ -482,7 +482,7 @@ int comm_verify_plans(iemic_ctx* c)
         for (const auto* ph : {&px, &py}) {
             std::map<int, int> ks, kr;
             for (const MsgD& mg : *ph) {
-                const int a = mg.send ? c->rank : mg.peer, b = mg.send ? mg.peer : c->rank;
+                const int a = mg.send ? c->sub.rank : mg.peer, b = mg.send ? mg.peer : c->sub.rank;
                 const int k = mg.send ? ks[b]++ : kr[a]++;
                 const double sg = mg.send ? 1.0 : -1.0;
                 double* e = t.data() + ((size_t)q * 2 * P + a) * P + b;

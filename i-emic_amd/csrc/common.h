@@ -339,18 +339,6 @@ struct iemic_ctx {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     int n = 0, m = 0, l = 0;
     int64_t ncell = 0, nrows = 0;    /* global cells / rows                               */
-    /* Decomp2D subdomain (TRIOS_Domain.C:81-195; stencil.h ext layout): process grid
-     * npx x npy, rank = py * npx + px, owned columns [ib0, ib1) and rows [jb0, jb1); hx x-halo
-     * columns when npx > 1; neighbours nb[W, E, S, N] (-1: none; W/E wrap when periodic) */
-    iemic::Sub sub;                  /* the same, as decomp.h computed it                  */
-    int rank = 0, nranks = 1;
-    int npx = 1, npy = 1, px = 0, py = 0;
-    int jb0 = 0, jb1 = 0, ib0 = 0, ib1 = 0, nx = 0, hx = 0;
-    int64_t xb = 0;                  /* first x-halo cell of an ext vector                */
-    int nb[4] = {-1, -1, -1, -1};
-    int64_t nloc = 0, nlrows = 0;    /* owned cells / rows                                */
-    int64_t next = 0, nerows = 0;    /* cells / rows of an ext vector (+ halo rows/columns) */
-    int64_t own0 = 0;                /* ext cell of the first owned cell                  */
     int64_t rowintcon = -1;          /* ext row of the integral condition if owned        */
     double int_correction = 0.0;     /* THCM::intCorrection_ (setIntCondCorrection)      */
     void* comm = nullptr;            /* ncclComm_t when nranks > 1 over RCCL              */
@@ -366,6 +354,7 @@ struct iemic_ctx {
     double comm_timeout_s = 300.0;
     int comm_checked = 0;
     iemic::host::Setup su;           /* grid tables, parameters, effective mask */
+    const iemic::Sub& sub = su;      /* this rank's Decomp2D subdomain and ext layout: su's record (decomp.h) */
     /* device tables */
     iemic::DevBuf<int> d_landm;
     iemic::DevBuf<double> d_tab;     /* cos_y | cos_yv | tan_yv | sin_yv | amh_y | bmh_y |
@@ -459,15 +448,6 @@ struct StreamGuard {
     iemic_ctx* c;
     ~StreamGuard() { if (c && c->stream) (void)dev_wait(c, nullptr, "return"); }
 };
-
-/* the subdomain layout handed to the structured-grid kernels */
-inline SubLay sub_lay(const iemic_ctx* c)
-{
-    SubLay X;
-    X.n = c->n; X.m = c->m; X.l = c->l; X.periodic = c->cfg.periodic;
-    X.jb0 = c->jb0; X.ib0 = c->ib0; X.nx = c->nx; X.hx = c->hx; X.xb = c->xb;
-    return X;
-}
 
 /* comm.hip: sums over the ranks (no-op for one rank) and halo exchanges.  A message is
  * nblk blocks of len doubles, stride doubles apart, from base + off; one exchange is a

@@ -160,8 +160,8 @@ CplPar cpl_par(const iemic_coupled* cm)
     const host::Setup& su = oc->su;
     CplPar K{};
     K.n = oc->n; K.m = oc->m; K.l = oc->l;
-    K.ib0 = oc->ib0; K.jb0 = oc->jb0; K.nx = oc->nx; K.mb = oc->jb1 - oc->jb0;
-    K.own0 = oc->own0;
+    K.ib0 = oc->sub.ib0; K.jb0 = oc->sub.jb0; K.nx = oc->sub.nx; K.mb = oc->sub.mb;
+    K.own0 = oc->sub.own0;
     const AtmPar& P = a->P;
     K.dTFQ = P.nuq * P.tdim / P.qdim * P.dqso * (1.0 - 0.0);
     K.pfac = (1.0 / P.total_area) * (P.tdim / P.qdim) * P.dqso * (1.0 - 0.0);
@@ -171,7 +171,7 @@ CplPar cpl_par(const iemic_coupled* cm)
     K.ct = oc->cfg.coupled_t;
     K.cs = oc->cfg.coupled_s;
     K.nus = su.nus;
-    K.sint_row = oc->rowintcon >= 0 ? oc->rowintcon - NUN * oc->own0 : -1;
+    K.sint_row = oc->rowintcon >= 0 ? oc->rowintcon - NUN * oc->sub.own0 : -1;
     return K;
 }
 
@@ -196,11 +196,11 @@ int cpl_sync(iemic_coupled* cm)
     if (rc) return rc;
     /* the atmosphere (replicated on every rank) sees the whole surface: each rank writes its
      * owned cells, the sum over the ranks fills the rest */
-    if (oc->nranks > 1) HIP_OK(hipMemsetAsync(a->d_sst.p, 0, sizeof(double) * nm, s));
+    if (oc->sub.nranks > 1) HIP_OK(hipMemsetAsync(a->d_sst.p, 0, sizeof(double) * nm, s));
     hipLaunchKernelGGL(k_sst, dim3((nm + 255) / 256), dim3(256), 0, s, cpl_par(cm), (const double*)oc->d_x.p,
                        a->d_sst.p);
     HIP_OK(hipGetLastError());
-    if (oc->nranks > 1 && (rc = allreduce_sum(oc, a->d_sst.p, nm))) return rc;
+    if (oc->sub.nranks > 1 && (rc = allreduce_sum(oc, a->d_sst.p, nm))) return rc;
     return 0;
 }
 
@@ -210,7 +210,7 @@ int cpl_surf(iemic_coupled* cm, const double* xo_packed, const double** tsurf)
 {
     iemic_ctx* oc = cm->oc;
     *tsurf = nullptr;
-    if (oc->nranks <= 1) return 0;
+    if (oc->sub.nranks <= 1) return 0;
     const int nm = oc->n * oc->m;
     hipStream_t s = oc->stream;
     double* t = cm->tsurf.p;
@@ -231,7 +231,7 @@ int cpl_apply(iemic_coupled* cm, const double* x, double* y)
     iemic_ctx* oc = cm->oc;
     iemic_atmos* a = cm->at;
     hipStream_t s = oc->stream;
-    const int64_t o = NUN * oc->own0, NL = cm->NL;
+    const int64_t o = NUN * oc->sub.own0, NL = cm->NL;
     const int nm = a->n * a->m;
     const CplPar K = cpl_par(cm);
     HIP_OK(hipMemcpyAsync(cm->xo.p + o, x, sizeof(double) * NL, hipMemcpyDeviceToDevice, s));
@@ -260,7 +260,7 @@ int cpl_prec(iemic_coupled* cm, const double* r, double* z, int use_prec)
     iemic_ctx* oc = cm->oc;
     iemic_atmos* a = cm->at;
     hipStream_t s = oc->stream;
-    const int64_t o = NUN * oc->own0, NL = cm->NL, NA = cm->NA;
+    const int64_t o = NUN * oc->sub.own0, NL = cm->NL, NA = cm->NA;
     const int nm = a->n * a->m;
     if (!use_prec) {
         HIP_OK(hipMemcpyAsync(z, r, sizeof(double) * (NL + NA), hipMemcpyDeviceToDevice, s));
@@ -290,8 +290,8 @@ int cpl_prec(iemic_coupled* cm, const double* r, double* z, int use_prec)
 void pack_host(const iemic_coupled* cm, const double* ref_vec, std::vector<double>& packed)
 {
     const iemic_ctx* oc = cm->oc;
-    const int64_t NL = cm->NL, NA = cm->NA, o = NUN * oc->own0;
-    std::vector<double> ext((size_t)oc->nerows, 0.0);
+    const int64_t NL = cm->NL, NA = cm->NA, o = NUN * oc->sub.own0;
+    std::vector<double> ext((size_t)oc->sub.nerows(), 0.0);
     oc->su.ref_to_ext(ref_vec, ext.data());
     packed.resize((size_t)(NL + NA));
     std::copy(ext.begin() + o, ext.begin() + o + NL, packed.begin());
@@ -301,8 +301,8 @@ void pack_host(const iemic_coupled* cm, const double* ref_vec, std::vector<doubl
 void unpack_host(const iemic_coupled* cm, const std::vector<double>& packed, double* ref_vec)
 {
     const iemic_ctx* oc = cm->oc;
-    const int64_t NL = cm->NL, o = NUN * oc->own0;
-    std::vector<double> ext((size_t)oc->nerows, 0.0);
+    const int64_t NL = cm->NL, o = NUN * oc->sub.own0;
+    std::vector<double> ext((size_t)oc->sub.nerows(), 0.0);
     std::copy(packed.begin(), packed.begin() + NL, ext.begin() + o);
     oc->su.ext_to_ref(ext.data(), ref_vec);
     std::copy(packed.begin() + NL, packed.end(), ref_vec + oc->nrows);
@@ -318,10 +318,10 @@ extern "C" int iemic_coupled_create(iemic_coupled** out, iemic_ctx* oc, iemic_at
     iemic_coupled* cm = new iemic_coupled();
     cm->oc = oc;
     cm->at = a;
-    cm->NL = oc->nlrows;
+    cm->NL = oc->sub.nlrows();
     cm->NA = a->dim;
     cm->NC = cm->NL + cm->NA;
-    const int64_t NE = oc->nerows;
+    const int64_t NE = oc->sub.nerows();
     rc = 0;
     rc |= cm->xo.alloc(NE);
     rc |= cm->yo.alloc(NE);

@@ -109,10 +109,10 @@ namespace {
 int cdot_dev(iemic_coupled* cm, const double* V, int64_t ld, int nv, const double* w, double* out)
 {
     hipStream_t s = cm->oc->stream;
-    const int64_t N = cm->oc->rank == 0 ? cm->NC : cm->NL;
+    const int64_t N = cm->oc->sub.rank == 0 ? cm->NC : cm->NL;
     hipLaunchKernelGGL(k_cdots, dim3(KB, nv + 1), dim3(256), 0, s, V, ld, nv, w, N, cm->part.p);
     hipLaunchKernelGGL(k_cfinal, dim3(nv + 1), dim3(256), 0, s, (const double*)cm->part.p, nv + 1, out);
-    if (cm->oc->nranks > 1) return allreduce_sum(cm->oc, out, nv + 1);
+    if (cm->oc->sub.nranks > 1) return allreduce_sum(cm->oc, out, nv + 1);
     return 0;
 }
 

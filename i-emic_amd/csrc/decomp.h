@@ -43,15 +43,35 @@ inline void part_of(int N, int np, int p, int& off, int& cnt)
     cnt = N / np + (p < N % np ? 1 : 0);
 }
 
-/* one rank's subdomain: process grid npx x npy, rank = py * npx + px, owned columns
- * [ib0, ib1) and rows [jb0, jb1), x-halo width hx (HALO when npx > 1), neighbours
- * nb[W, E, S, N] (-1: none; W/E wrap on a periodic grid) */
+/* One rank's subdomain, the only host statement of it (sub_init fills it; Setup, the
+ * context, the exchange plans and the kernel-argument builders read it): global grid
+ * n x m x l, process grid npx x npy, rank = py * npx + px, owned columns [ib0, ib1) and
+ * rows [jb0, jb1), x-halo width hx (HALO when npx > 1), neighbours nb[W, E, S, N] (-1:
+ * none; W/E wrap on a periodic grid), and the sizes of the ext layout (stencil.h) */
 struct Sub {
+    int n = 0, m = 0, l = 0, periodic = 0;
     int rank = 0, nranks = 1, npx = 1, npy = 1, px = 0, py = 0;
-    int ib0 = 0, ib1 = 0, jb0 = 0, jb1 = 0, nx = 0, mb = 0, hx = 0, l = 0;
+    int ib0 = 0, ib1 = 0, jb0 = 0, jb1 = 0, nx = 0, mb = 0, hx = 0;
     int64_t xb = 0;                   /* first x-halo cell of an ext vector           */
+    int64_t nloc = 0, next = 0;       /* owned cells, cells of an ext vector          */
+    int64_t own0 = 0;                 /* ext cell of the first owned cell             */
     int nb[4] = {-1, -1, -1, -1};
+    int64_t nlrows() const { return NUN * nloc; }   /* owned rows                     */
+    int64_t nerows() const { return NUN * next; }   /* rows of an ext vector          */
 };
+
+/* the sizes of the ext layout (stencil.h) from the owned ranges; xsplit: the x direction is
+ * split over several ranks, so the layout has the x halo */
+inline void sub_sizes(Sub& d, bool xsplit)
+{
+    d.nx = d.ib1 - d.ib0;
+    d.mb = d.jb1 - d.jb0;
+    d.hx = xsplit ? HALO : 0;
+    d.nloc = (int64_t)d.nx * d.l * d.mb;
+    d.xb = (int64_t)d.nx * d.l * (d.mb + 2 * HALO);
+    d.next = d.xb + (int64_t)2 * d.hx * d.l * (d.mb + 2 * HALO);
+    d.own0 = (int64_t)HALO * d.l * d.nx;
+}
 
 /* 0, or a message for a decomposition the layout cannot hold */
 inline const char* sub_init(Sub& d, int n, int m, int l, int periodic, int rank, int nranks, int npx)
@@ -76,15 +96,26 @@ inline const char* sub_init(Sub& d, int n, int m, int l, int periodic, int rank,
     part_of(m, npy, d.py, d.jb0, d.mb);
     d.ib1 = d.ib0 + d.nx;
     d.jb1 = d.jb0 + d.mb;
+    d.n = n;
+    d.m = m;
     d.l = l;
-    d.hx = npx > 1 ? HALO : 0;
-    d.xb = (int64_t)d.nx * l * (d.mb + 2 * HALO);
+    d.periodic = periodic;
+    sub_sizes(d, npx > 1);
     const bool wrap = periodic && npx > 1;
     d.nb[0] = d.px > 0 ? rank - 1 : (wrap ? rank + npx - 1 : -1);
     d.nb[1] = d.px < npx - 1 ? rank + 1 : (wrap ? rank - (npx - 1) : -1);
     d.nb[2] = d.py > 0 ? rank - npx : -1;
     d.nb[3] = d.py < npy - 1 ? rank + npx : -1;
     return nullptr;
+}
+
+/* the subdomain layout handed to the structured-grid kernels */
+inline SubLay sub_lay(const Sub& d)
+{
+    SubLay X;
+    X.n = d.n; X.m = d.m; X.l = d.l; X.periodic = d.periodic;
+    X.jb0 = d.jb0; X.ib0 = d.ib0; X.nx = d.nx; X.hx = d.hx; X.xb = d.xb;
+    return X;
 }
 
 /* one message: nblk blocks of len doubles, stride doubles apart, from offset off */

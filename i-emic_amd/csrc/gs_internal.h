@@ -103,12 +103,13 @@ __device__ __forceinline__ double bts_row(const double* __restrict__ val, const 
 
 }  // namespace
 
-static Lay lay_of(const iemic_ctx* c)
+/* the record plus the plane stride of the planar dynamics vectors (next) */
+static Lay lay_of(const Sub& S)
 {
     Lay L;
-    L.n = c->n; L.m = c->m; L.l = c->l; L.periodic = c->cfg.periodic; L.jb0 = c->jb0;
-    L.ib0 = c->ib0; L.nx = c->nx; L.hx = c->hx; L.xb = c->xb;
-    L.nloc = c->nloc; L.own0 = c->own0; L.ps = c->next;
+    L.n = S.n; L.m = S.m; L.l = S.l; L.periodic = S.periodic; L.jb0 = S.jb0;
+    L.ib0 = S.ib0; L.nx = S.nx; L.hx = S.hx; L.xb = S.xb;
+    L.nloc = S.nloc; L.own0 = S.own0; L.ps = S.next;
     return L;
 }
 /* blocks launched for nwg workgroups dealt to the 8 XCDs in contiguous runs (xcd_block) */

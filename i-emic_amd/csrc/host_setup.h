@@ -22,6 +22,7 @@
 
 #include "../../include/iemic.h"
 #include "stencil.h"
+#include "decomp.h"
 
 namespace iemic {
 namespace host {
@@ -58,7 +59,10 @@ inline double wfun(double yy)
            0.5 * (1 - std::tanh(10 * (pi_ / 2 - std::fabs(yy))));
 }
 
-struct Setup {
+/* the set-up of one rank's subdomain: the layout record (decomp.h Sub: grid sizes, owned
+ * ranges, x halo and the ext-layout sizes) is its base, so the helpers below read the
+ * record's fields and nothing here restates them */
+struct Setup : Sub {
     iemic_grid cfg;
     /* m_mix flags (mix_imp.f vmix_init 58-109): Mixing 1 mixes T and S from the start;
      * Mixing 2 decides at the first evaluation (vmix_control, 131-166) */
@@ -75,7 +79,6 @@ struct Setup {
         return par[P_MIXP] == 0.0 && par[P_MKAP] == 0.0 &&
                (1.0 - par[P_ALPC]) * par[P_ENER] * par[P_PE_V] == 0.0;
     }
-    int n = 0, m = 0, l = 0;
     double xmin = 0, xmax = 0, ymin = 0, ymax = 0, dx = 0, dy = 0, dz = 0;
     std::vector<double> y, yv, dfzT, dfzW;
     std::vector<int> landm;          /* local mask after init_ border handling */
@@ -103,11 +106,6 @@ struct Setup {
     double dedt() const { return lvsc * eta_a * qdim_a * (1.0 / qdim_a) * dqso; }
     int rowintcon_ref = -1;          /* reference (global) row of the integral condition */
     int64_t rowintcon = -1;          /* its ext row when this band owns it, else -1       */
-    /* owned subdomain [ib0, ib1) x [jb0, jb1) of the Decomp2D process grid, full depth;
-     * hx = HALO x-halo columns when the x direction is split (stencil.h ext layout) */
-    int jb0 = 0, jb1 = 0, ib0 = 0, ib1 = 0, nx = 0, hx = 0;
-    int64_t xb = 0;                  /* first x-halo cell                                 */
-    int64_t nloc = 0, next = 0;      /* owned cells, cells of an ext vector               */
 
     /* ---- layout helpers (see the ext layout in stencil.h) ------------------------- */
     /* ext cell of 0-based global (i, j, k), j within the halo rows, i within the x halo
@@ -118,7 +116,6 @@ struct Setup {
         return xcell(r, xlocal(i, n, ib0, nx, hx, hx ? cfg.periodic : 0), nx, hx, xb);
     }
     int64_t ref_cell(int i, int j, int k) const { return ((int64_t)k * m + j) * n + i; }
-    int64_t own0() const { return (int64_t)HALO * l * nx; }       /* first owned ext cell  */
     /* owned-local index lc -> 0-based (i, j, k) */
     void owned_ijk(int64_t lc, int& i, int& j, int& k) const
     {
@@ -153,22 +150,24 @@ struct Setup {
     }
     bool owns(int i, int j) const { return j >= jb0 && j < jb1 && i >= ib0 && i < ib1; }
 
-    /* sub0/sub1: owned columns [sub0[0], sub1[0]) and rows [sub0[1], sub1[1]); xsplit: the x
-     * direction is split over several ranks (x halo in the layout) */
+    /* a window of the grid that is no rank's subdomain (a latitude band of the CPU harness):
+     * the one-rank record narrowed to columns [sub0[0], sub1[0]) and rows [sub0[1], sub1[1]),
+     * with the x halo when xsplit */
     void init(const iemic_grid& g, const int* landm_in, const int* sub0 = nullptr, const int* sub1 = nullptr,
               int xsplit = 0)
     {
+        Sub d;
+        (void)sub_init(d, g.n, g.m, g.l, g.periodic, 0, 1, 1);
+        if (sub0) d.ib0 = sub0[0], d.jb0 = sub0[1];
+        if (sub1) d.ib1 = sub1[0], d.jb1 = sub1[1];
+        sub_sizes(d, xsplit != 0);
+        init(g, landm_in, d);
+    }
+    /* d: this rank's subdomain of grid g, from sub_init */
+    void init(const iemic_grid& g, const int* landm_in, const Sub& d)
+    {
         cfg = g;
-        n = g.n; m = g.m; l = g.l;
-        ib0 = sub0 ? sub0[0] : 0;
-        ib1 = sub1 ? sub1[0] : n;
-        jb0 = sub0 ? sub0[1] : 0;
-        jb1 = sub1 ? sub1[1] : m;
-        nx = ib1 - ib0;
-        hx = xsplit ? HALO : 0;
-        nloc = (int64_t)nx * l * (jb1 - jb0);
-        xb = (int64_t)nx * l * (jb1 - jb0 + 2 * HALO);
-        next = xb + (int64_t)2 * hx * l * (jb1 - jb0 + 2 * HALO);
+        static_cast<Sub&>(*this) = d;
         xmin = g.xmin * pi_ / 180.0;
         xmax = g.xmax * pi_ / 180.0;
         ymin = g.ymin * pi_ / 180.0;
@@ -324,7 +323,7 @@ struct Setup {
     /* coefficients in the ext layout (owned S rows), for the device */
     std::vector<double> intcond_coeff() const
     {
-        std::vector<double> ic((size_t)NUN * next, 0.0);
+        std::vector<double> ic((size_t)nerows(), 0.0);
         for (int64_t lc = 0; lc < nloc; lc++) {
             int i, j, k;
             owned_ijk(lc, i, j, k);

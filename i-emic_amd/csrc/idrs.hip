@@ -58,7 +58,7 @@ int idrs(iemic_ctx* c, const double* b, double* x, const iemic_krylov* opt, iemi
     const double angle = opt->idr_angle > 0.0 ? opt->idr_angle : 0.7;
     const double mp = 1e-13;
     const int maxit = std::max(1, opt->krylov_dim * (opt->max_restarts + 1));
-    const int64_t NE = c->nerows, o = NUN * c->own0, NL = c->nlrows;
+    const int64_t NE = c->sub.nerows(), o = NUN * c->sub.own0, NL = c->sub.nlrows();
     /* vectors: P (s) | U (s) | G (s) | t | r | v  in the Krylov basis storage */
     int rc = ensure_krylov(c, 3 * s + 3);
     if (rc) return rc;
@@ -77,7 +77,7 @@ int idrs(iemic_ctx* c, const double* b, double* x, const iemic_krylov* opt, iemi
     const unsigned GR = grid_for(NL);
     /* shadow space (createP: random, orthonormalised in order) */
     hipLaunchKernelGGL(k_idr_random, dim3((unsigned)((NL + 255) / 256)), dim3(256), 0, c->stream, P, NE, s, NL,
-                       o, c->n, c->m, c->l, c->jb0, c->ib0, c->nx);
+                       o, c->n, c->m, c->l, c->sub.jb0, c->sub.ib0, c->sub.nx);
     for (int j = 0; j < s; j++) {
         std::vector<double> al(j + 1);
         if (j > 0 && (rc = mdot_host(c, P + o, NE, j, Pi(j) + o, al.data()))) return rc;

@@ -375,7 +375,7 @@ __global__ void __launch_bounds__(256) k_mupdate_add(const double* __restrict__ 
 int mdot_host(iemic_ctx* c, const double* V, int64_t ldv, int nvec, const double* w,
               double* out, const double* ea, const double* eb)
 {
-    const int64_t N = c->nlrows;
+    const int64_t N = c->sub.nlrows();
     const int nout = nvec + (ea ? 1 : 0);
     hipLaunchKernelGGL(k_mdot, dim3(RED_BLOCKS, nout), dim3(256), 0, c->stream, V, ldv, nvec, w, N,
                        c->d_part.p, ea, eb);
@@ -393,14 +393,14 @@ int mdot_host(iemic_ctx* c, const double* V, int64_t ldv, int nvec, const double
 /* a . b over the owned rows of two ext vectors, summed over the ranks (error code) */
 int dot_owned(iemic_ctx* c, const double* a, const double* b, double* out)
 {
-    const int64_t o = NUN * c->own0;
+    const int64_t o = NUN * c->sub.own0;
     return mdot_host(c, a + o, 0, 1, b + o, out);
 }
 
 /* a . b over the owned rows of two ext vectors, summed over the ranks */
 double dot(iemic_ctx* c, const double* a, const double* b, int64_t)
 {
-    const int64_t o = NUN * c->own0;
+    const int64_t o = NUN * c->sub.own0;
     double r = 0.0;
     if (mdot_host(c, a + o, 0, 1, b + o, &r)) return NAN;
     return r;
@@ -412,7 +412,7 @@ double dot(iemic_ctx* c, const double* a, const double* b, int64_t)
 static int orth_pass(iemic_ctx* c, const double* V, int64_t ldv, int nvec, double* w, double* h,
                      double* ww0, double* ww1)
 {
-    const int64_t N = c->nlrows;
+    const int64_t N = c->sub.nlrows();
     hipLaunchKernelGGL(k_mdot, dim3(RED_BLOCKS, nvec + 1), dim3(256), 0, c->stream, V, ldv, nvec,
                        w, N, c->d_part.p, (const double*)w);
     hipLaunchKernelGGL(k_mdot_final, dim3(nvec + 1), dim3(256), 0, c->stream, c->d_part.p,
@@ -438,7 +438,7 @@ static int orth_pass(iemic_ctx* c, const double* V, int64_t ldv, int nvec, doubl
 int ensure_krylov(iemic_ctx* c, int m, int64_t nc)
 {
     Krylov& k = c->kr;
-    const int64_t N = c->nerows;
+    const int64_t N = c->sub.nerows();
     int rc = 0;
     if (k.m < m || !k.Z.p) {
         k.zclean = 0;
@@ -531,7 +531,7 @@ int fgmres(iemic_ctx* c, const double* b, double* x, const iemic_krylov* opt, ie
 {
     /* vectors are ext-layout (stride NE); kernels touch the owned rows [o, o + NL) */
     const int m = std::max(1, std::min(opt->krylov_dim, MAX_KRYLOV));
-    const int64_t NE = c->nerows, o = NUN * c->own0, NL = c->nlrows;
+    const int64_t NE = c->sub.nerows(), o = NUN * c->sub.own0, NL = c->sub.nlrows();
     /* DCGS2 with the block GS: the Arnoldi basis on the active cells only.  Identity rows of J
      * (all rows of a land cell, some of an ocean cell) are identity rows of the preconditioner
      * too, so with a right-hand side that is zero on them every Krylov vector is exactly zero
@@ -621,7 +621,8 @@ int fgmres(iemic_ctx* c, const double* b, double* x, const iemic_krylov* opt, ie
     for (int cycle = 0; beta > 0.0 && cycle <= opt->max_restarts; cycle++) {
         const int it_c0 = it;
         if (cmp)
-            hipLaunchKernelGGL(k_cgather, dim3(GC), dim3(256), 0, c->stream, r, gs.act.act.p, NC, c->own0, 1.0 / beta, Vc);
+            hipLaunchKernelGGL(k_cgather, dim3(GC), dim3(256), 0, c->stream, r, gs.act.act.p, NC, c->sub.own0,
+                               1.0 / beta, Vc);
         else
             hipLaunchKernelGGL(k_scale_copy, dim3(G), dim3(256), 0, c->stream, r + o, 1.0 / beta, V + o, NL);
         hess.reset(beta);
@@ -747,7 +748,7 @@ int fgmres(iemic_ctx* c, const double* b, double* x, const iemic_krylov* opt, ie
                 if (jj < m)
                     hipLaunchKernelGGL(k_dcgs_update, dim3((unsigned)std::min<int64_t>(4096, (NQ / 2 + 255) / 256)), dim3(256), 0, c->stream, Q, LQ, nv,
                                        c->d_hbuf.p + RED_ROWS, u, wv, NQ, cmp ? (const int*)gs.act.act.p : nullptr,
-                                       c->own0, (int64_t)c->next, cmp ? gs.rrP.p : nullptr);
+                                       c->sub.own0, (int64_t)c->sub.next, cmp ? gs.rrP.p : nullptr);
                 return 0;
             };
             if ((rc = enqueue(0))) return rc;

@@ -112,15 +112,15 @@ int prec_compute(iemic_ctx* c, const iemic_krylov* opt)
     }
     c->gs.kind = opt ? opt->prec : 1;
     if (c->gs.kind == 2) return gs_compute(c, opt);
-    if (c->gs.dinv.n < (size_t)36 * c->nloc) {
-        if (c->gs.dinv.alloc((size_t)36 * c->nloc)) {
+    if (c->gs.dinv.n < (size_t)36 * c->sub.nloc) {
+        if (c->gs.dinv.alloc((size_t)36 * c->sub.nloc)) {
             set_error("prec_compute: out of memory");
             return IEMIC_ENOMEM;
         }
     }
     HIP_OK(hipMemsetAsync(c->d_red.p, 0, sizeof(int), c->stream));
-    hipLaunchKernelGGL(k_bj_compute, dim3((unsigned)((c->nloc + 127) / 128)), dim3(128), 0, c->stream,
-                       c->d_val.p, c->nloc, c->gs.dinv.p, (int*)c->d_red.p);
+    hipLaunchKernelGGL(k_bj_compute, dim3((unsigned)((c->sub.nloc + 127) / 128)), dim3(128), 0, c->stream,
+                       c->d_val.p, c->sub.nloc, c->gs.dinv.p, (int*)c->d_red.p);
     HIP_OK(hipGetLastError());
     c->gs.ready = 1;
     return 0;
@@ -145,9 +145,9 @@ int prec_apply(iemic_ctx* c, const double* r, double* z)
         return IEMIC_ESTATE;
     }
     if (c->gs.kind == 2) return gs_apply(c, r, z);
-    const int64_t o = NUN * c->own0;
-    hipLaunchKernelGGL(k_bj_apply, dim3((unsigned)((c->nloc + 255) / 256)), dim3(256), 0, c->stream,
-                       c->gs.dinv.p, c->nloc, r + o, z + o);
+    const int64_t o = NUN * c->sub.own0;
+    hipLaunchKernelGGL(k_bj_apply, dim3((unsigned)((c->sub.nloc + 255) / 256)), dim3(256), 0, c->stream,
+                       c->gs.dinv.p, c->sub.nloc, r + o, z + o);
     HIP_OK(hipGetLastError());
     return 0;
 }

@@ -1152,7 +1152,7 @@ int build_structure(iemic_ctx* c, const std::vector<double>& flags)
 
 /* colour-compacted T/S sweeps: the owned cells of one colour are every other cell of a
  * row (even n, nx and ib0) */
-static bool ts_compact(const iemic_ctx* c) { return (c->n & 1) == 0 && (c->nx & 1) == 0 && (c->ib0 & 1) == 0; }
+static bool ts_compact(const iemic_ctx* c) { return (c->n & 1) == 0 && (c->sub.nx & 1) == 0 && (c->sub.ib0 & 1) == 0; }
 
 /* the T/S block solve: right-hand side rr_TS - A_TS,D z_D from the dynamics iterate zd (the
  * planar zP for the multigrid, the AoS output for the sweeps), then ts_mg V-cycles
@@ -1162,17 +1162,17 @@ static int ts_solve(iemic_ctx* c, const double* zd, double* z, bool out, bool si
 {
     BlockGS& gs = c->gs;
     if (gs.ts_mg > 0) return ts_mg_solve(c, zd, z, out, side);
-    const Lay L = lay_of(c);
+    const Lay L = lay_of(c->sub);
     const int n = c->n;
     hipStream_t s = c->stream;
-    const unsigned gc = (unsigned)((c->nloc + 255) / 256);
+    const unsigned gc = (unsigned)((c->sub.nloc + 255) / 256);
     const int nsw = std::max(1, gs.ts_sweeps);
     if (ts_compact(c)) {
         /* colour-compacted symmetric red-black sweeps */
-        const int nblk = (int)((c->nloc + 63) / 64);
+        const int nblk = (int)((c->sub.nloc + 63) / 64);
         hipLaunchKernelGGL(k_gs_bts2, dim3(8u * (unsigned)((nblk + 7) / 8)), dim3(128), 0, s, gs.act.vp,
                            gs.known.p, gs.kmask.p, gs.rr.p, z, gs.sw.bc.p, gs.sw.zt.p, gs.sw.zs.p, L, gs.sw.bts.p, nblk);
-        const unsigned gh = (unsigned)((c->nloc / 2 + 255) / 256);
+        const unsigned gh = (unsigned)((c->sub.nloc / 2 + 255) / 256);
         const int seq[4] = {0, 1, 1, 0};
         for (int sw = 0; sw < nsw; sw++)
             for (int h = 0; h < 4; h++)
@@ -1190,7 +1190,7 @@ static int ts_solve(iemic_ctx* c, const double* zd, double* z, bool out, bool si
         for (int sw = 0; sw < nsw; sw++)
             for (int h = 0; h < ns; h++)
                 hipLaunchKernelGGL(k_gs_ts_half, dim3(gc), dim3(256), 0, s, gs.sw.tsoff.p, gs.known.p,
-                                   gs.sw.tsinv.p, gs.sw.bts.p, z, L, c->next, seq[h]);
+                                   gs.sw.tsinv.p, gs.sw.bts.p, z, L, c->sub.next, seq[h]);
     }
     HIP_OK(hipGetLastError());
     return 0;
@@ -1203,7 +1203,7 @@ static int ts_solve(iemic_ctx* c, const double* zd, double* z, bool out, bool si
 static int gs_reserve_cells(iemic_ctx* c)
 {
     BlockGS& gs = c->gs;
-    const int64_t NE = c->nerows, next = c->next;
+    const int64_t NE = c->sub.nerows(), next = c->sub.next;
     if (gs.known.n >= (size_t)NE) return 0;
     int rc = 0;
     rc |= gs.known.alloc(NE);
@@ -1214,9 +1214,9 @@ static int gs_reserve_cells(iemic_ctx* c)
     rc |= gs.sw.bts.alloc(NE);
     rc |= gs.kmask.alloc((size_t)2 * next);
     rc |= gs.sw.tsoff.alloc((size_t)TS_NC * next);
-    rc |= gs.sw.tsc.alloc((size_t)TS_NC * c->nloc);
-    rc |= gs.sw.tic.alloc((size_t)4 * c->nloc);
-    rc |= gs.sw.bc.alloc((size_t)2 * c->nloc);
+    rc |= gs.sw.tsc.alloc((size_t)TS_NC * c->sub.nloc);
+    rc |= gs.sw.tic.alloc((size_t)4 * c->sub.nloc);
+    rc |= gs.sw.bc.alloc((size_t)2 * c->sub.nloc);
     rc |= gs.sw.zt.alloc(next);
     rc |= gs.sw.zs.alloc(next);
     rc |= gs.tsdiag.alloc((size_t)4 * next);
@@ -1240,16 +1240,16 @@ static int gs_reserve_cells(iemic_ctx* c)
 static int gs_identity_flags(iemic_ctx* c)
 {
     BlockGS& gs = c->gs;
-    const int64_t NE = c->nerows, next = c->next;
+    const int64_t NE = c->sub.nerows(), next = c->sub.next;
     const unsigned gN = (unsigned)std::min<int64_t>((NE + 255) / 256, 4096);
     int rc;
     HIP_OK(hipMemsetAsync(gs.known.p, 1, NE, c->stream));     /* outer halo rows: identity */
     /* the planar iterate: 0 on the rows no pass writes (identity rows of this Jacobian, T/S) */
     HIP_OK(hipMemsetAsync(gs.zP.p, 0, sizeof(double) * NE, c->stream));
-    hipLaunchKernelGGL(k_known, dim3(blocks_for(c->nloc)), dim3(256), 0, c->stream, c->d_val.p, lay_of(c),
+    hipLaunchKernelGGL(k_known, dim3(blocks_for(c->sub.nloc)), dim3(256), 0, c->stream, c->d_val.p, lay_of(c->sub),
                        (int64_t)c->rowintcon, gs.known.p);
     HIP_OK(hipGetLastError());
-    if (c->nranks > 1) {
+    if (c->sub.nranks > 1) {
         /* the neighbours' flags of the adjacent latitude rows */
         hipLaunchKernelGGL(k_u8_to_d, dim3(gN), dim3(256), 0, c->stream, gs.known.p, gs.rr.p, NE);
         if ((rc = halo_exchange_w(c, gs.rr.p, NUN, 1))) return rc;
@@ -1268,8 +1268,8 @@ static int gs_global_structure(iemic_ctx* c)
     const size_t nf = (size_t)2 * c->n * c->m;
     if (gs.flags_d.reserve(nf)) return IEMIC_ENOMEM;
     HIP_OK(hipMemsetAsync(gs.flags_d.p, 0, sizeof(double) * nf, c->stream));
-    hipLaunchKernelGGL(k_band_flags, dim3((unsigned)((c->nloc / c->l + 255) / 256)), dim3(256), 0, c->stream,
-                       gs.known.p, lay_of(c), gs.flags_d.p);
+    hipLaunchKernelGGL(k_band_flags, dim3((unsigned)((c->sub.nloc / c->l + 255) / 256)), dim3(256), 0, c->stream,
+                       gs.known.p, lay_of(c->sub), gs.flags_d.p);
     if ((rc = allreduce_sum(c, gs.flags_d.p, (int)nf))) return rc;
     std::vector<double> flags(nf);
     if ((rc = d2h(c, flags.data(), gs.flags_d.p, sizeof(double) * nf))) return rc;
@@ -1282,9 +1282,9 @@ static int gs_global_structure(iemic_ctx* c)
 static int gs_cell_factors(iemic_ctx* c)
 {
     BlockGS& gs = c->gs;
-    const Lay L = lay_of(c);
-    const int64_t next = c->next;
-    const unsigned gc = blocks_for(c->nloc);
+    const Lay L = lay_of(c->sub);
+    const int64_t next = c->sub.next;
+    const unsigned gc = blocks_for(c->sub.nloc);
     int rc;
     if (gs.gslot.n < (size_t)GSL * next) {
         if (gs.gslot.alloc((size_t)GSL * next)) return IEMIC_ENOMEM;
@@ -1294,7 +1294,7 @@ static int gs_cell_factors(iemic_ctx* c)
                        L, (int64_t)c->rowintcon, c->cfg.int_sign, c->d_intc.p, gs.uvinv.p,
                        gs.sw.tsinv.p, gs.pw.p, gs.tsdiag.p, next);
     hipLaunchKernelGGL(k_gslot_pack, dim3(gc), dim3(256), 0, c->stream, c->d_val.p, L, gs.gslot.p);
-    if (c->nranks > 1) {
+    if (c->sub.nranks > 1) {
         if ((rc = halo_exchange_w(c, gs.uvinv.p, 4, 1))) return rc;
         if ((rc = halo_exchange_w(c, gs.gslot.p, GSL, 1))) return rc;
     }
@@ -1306,11 +1306,11 @@ static int gs_cell_factors(iemic_ctx* c)
 static int gs_apply_tables(iemic_ctx* c)
 {
     BlockGS& gs = c->gs;
-    const Lay L = lay_of(c);
-    const int64_t next = c->next;
-    const unsigned gc = blocks_for(c->nloc);
+    const Lay L = lay_of(c->sub);
+    const int64_t next = c->sub.next;
+    const unsigned gc = blocks_for(c->sub.nloc);
     if (c->l <= 64) {
-        const int64_t ncolb = c->nloc / c->l;
+        const int64_t ncolb = c->sub.nloc / c->l;
         if (gs.rcol.reserve((size_t)(ncolb * RC_NE * c->l))) return IEMIC_ENOMEM;
         hipLaunchKernelGGL(k_rcol_uvp, dim3(blocks_for(ncolb * c->l)), dim3(256), 0, c->stream, c->d_val.p,
                            gs.known.p, gs.uvinv.p, gs.pw.p, gs.rcol.p, L);
@@ -1318,7 +1318,7 @@ static int gs_apply_tables(iemic_ctx* c)
                            gs.gslot.p, gs.rcol.p, L);
     }
     hipLaunchKernelGGL(k_knownmask, dim3(gc), dim3(256), 0, c->stream, c->d_val.p, gs.known.p,
-                       gs.kmask.p, L, c->jb1);
+                       gs.kmask.p, L, c->sub.jb1);
     hipLaunchKernelGGL(k_ts_compact, dim3(gc), dim3(256), 0, c->stream, c->d_val.p, gs.known.p,
                        gs.sw.tsoff.p, L, next, (int64_t)c->rowintcon);
     if (ts_compact(c))
@@ -1335,10 +1335,10 @@ static int gs_schur_factor(iemic_ctx* c)
     int rc;
     const int NC = c->n * c->m;
     HIP_OK(hipMemsetAsync(gs.S9.p, 0, sizeof(double) * 9 * (size_t)NC, c->stream));
-    const int64_t nt = (int64_t)c->nx * (c->jb1 - c->jb0) * 9;
+    const int64_t nt = (int64_t)c->sub.nx * c->sub.mb * 9;
     hipLaunchKernelGGL(k_schur_build, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, c->stream,
                        c->d_val.p, gs.known.p, gs.uvinv.p, gs.gslot.p, gs.pw.p, gs.col_of_ij.p,
-                       gs.pinned.p, lay_of(c), c->jb1, gs.S9.p);
+                       gs.pinned.p, lay_of(c->sub), c->sub.jb1, gs.S9.p);
     if ((rc = allreduce_sum(c, gs.S9.p, 9 * NC))) return rc;
     if ((rc = cr_factor(c, gs.cr, gs.S9.p, gs.col_of_ij.p))) return rc;
     return cr_check(c, gs.cr);
@@ -1349,7 +1349,7 @@ int gs_compute(iemic_ctx* c, const iemic_krylov* opt)
     BlockGS& gs = c->gs;
     gs.ready = 0;
     gs.ts_sweeps = opt ? std::max(0, opt->ts_sweeps) : 3;
-    const int64_t NE = c->nerows;
+    const int64_t NE = c->sub.nerows();
     if (c->l > 64) {
         set_error("block GS: more than 64 levels per column (the column kernels hold a column in one workgroup)");
         return IEMIC_EINVAL;
@@ -1413,26 +1413,26 @@ static int dyn_solve(iemic_ctx* c, const double* rr, double* z, double* zo = nul
                      double* zaos = nullptr, bool rr_halo = false, bool schur = true)
 {
     BlockGS& gs = c->gs;
-    const Lay L = lay_of(c);
-    const unsigned gc = (unsigned)((c->nloc + 255) / 256);
+    const Lay L = lay_of(c->sub);
+    const unsigned gc = (unsigned)((c->sub.nloc + 255) / 256);
     hipStream_t s = c->stream;
-    const bool band = c->nranks > 1;
+    const bool band = c->sub.nranks > 1;
     int rc = 0;
-    const int64_t ncolb = c->nloc / c->l;                        /* water columns of the band */
+    const int64_t ncolb = c->sub.nloc / c->l;                        /* water columns of the band */
     const int Pl = mg_lanes(c->l);                               /* l <= 64 (gs_compute) */
     /* transposed column kernels: 1024 / Pl columns of one row per workgroup of 1024 threads */
     const int cti = 1024 / Pl;
-    const unsigned gct = xcd_grid(((c->nx + cti - 1) / cti) * (ncolb / c->nx));
+    const unsigned gct = xcd_grid(((c->sub.nx + cti - 1) / cti) * (ncolb / c->sub.nx));
     const dim3 bct(1024u);
-    const int64_t ps = c->next;
+    const int64_t ps = c->sub.next;
     /* ptil and the Schur right-hand side in one column pass (rcol), the U/V points once
      * after the Schur solve, then p and w */
     /* latitude bands: after the one exchange of rr, the pass computes ptil on both halo rows
      * and the U/V points of the south one itself (the halo-filled gslot holds their
      * couplings) instead of exchanging ptil and uv (3 -> 1 exchange batch per pass) */
-    const bool hrow = band && c->npx == 1;
+    const bool hrow = band && c->sub.npx == 1;
     const double* gsl = hrow ? gs.gslot.p : nullptr;
-    const unsigned gcth = hrow ? xcd_grid(((c->nx + cti - 1) / cti) * (ncolb / c->nx + 2)) : gct;
+    const unsigned gcth = hrow ? xcd_grid(((c->sub.nx + cti - 1) / cti) * (ncolb / c->sub.nx + 2)) : gct;
     if (band && !rr_halo && (rc = halo_exchange_planar(c, const_cast<double*>(rr), NUN, ps, 1))) return rc;   /* rr around the band */
     with_lanes(Pl, [&](auto p) {
         auto kp = schur ? k_gs_ptil_rcol<LANES_OF(p), true> : k_gs_ptil_rcol<LANES_OF(p), false>;
@@ -1450,8 +1450,8 @@ static int dyn_solve(iemic_ctx* c, const double* rr, double* z, double* zo = nul
     }
     if (schur && (rc = cr_solve(c, gs.cr, sb, gs.colv2.p, s, gs.colvT.p))) return rc;
     const bool al = gs.act.act.p && gs.act.nact > 0;
-    const int64_t nown = al ? gs.act.nact : c->nloc;
-    const unsigned gcu = (unsigned)((nown + (hrow ? (int64_t)c->l * c->nx : 0) + 255) / 256);
+    const int64_t nown = al ? gs.act.nact : c->sub.nloc;
+    const unsigned gcu = (unsigned)((nown + (hrow ? (int64_t)c->l * c->sub.nx : 0) + 255) / 256);
     hipLaunchKernelGGL(k_gs_uvp, dim3(gcu), dim3(256), 0, s, gs.act.vp, gs.knP.p, gs.uvinv.p,
                        rr, pbT, z, L, zo, omega, zaos, gsl, al ? gs.act.act.p : nullptr, nown);
     if (band && !hrow && (rc = halo_exchange_planar(c, z, NUN, ps, 1))) return rc;   /* uv below the band */
@@ -1475,8 +1475,8 @@ int gs_time_parts(iemic_ctx* c, int nrep, double* us)
         set_error("gs_time_parts: the block GS preconditioner is not computed");
         return IEMIC_ESTATE;
     }
-    if (c->nranks > 1) {   /* parts 2 and 3 exchange halos: not callable on one rank alone */
-        set_error("gs_time_parts: one-rank diagnostic, the context has " + std::to_string(c->nranks) + " ranks");
+    if (c->sub.nranks > 1) {   /* parts 2 and 3 exchange halos: not callable on one rank alone */
+        set_error("gs_time_parts: one-rank diagnostic, the context has " + std::to_string(c->sub.nranks) + " ranks");
         return IEMIC_EINVAL;
     }
     hipStream_t s = c->stream;
@@ -1484,11 +1484,11 @@ int gs_time_parts(iemic_ctx* c, int nrep, double* us)
     if (ev.create()) return IEMIC_EDEVICE;
     const hipEvent_t e0 = ev.a, e1 = ev.b;
     double* z = c->d_tmp2.p;
-    HIP_OK(hipMemsetAsync(c->d_tmp1.p, 0, sizeof(double) * c->nerows, s));
-    HIP_OK(hipMemsetAsync(z, 0, sizeof(double) * c->nerows, s));
-    HIP_OK(hipMemsetAsync(gs.rr.p, 0, sizeof(double) * c->nerows, s));
-    HIP_OK(hipMemsetAsync(gs.rrP.p, 0, sizeof(double) * c->nerows, s));
-    HIP_OK(hipMemsetAsync(gs.zP.p, 0, sizeof(double) * c->nerows, s));
+    HIP_OK(hipMemsetAsync(c->d_tmp1.p, 0, sizeof(double) * c->sub.nerows(), s));
+    HIP_OK(hipMemsetAsync(z, 0, sizeof(double) * c->sub.nerows(), s));
+    HIP_OK(hipMemsetAsync(gs.rr.p, 0, sizeof(double) * c->sub.nerows(), s));
+    HIP_OK(hipMemsetAsync(gs.rrP.p, 0, sizeof(double) * c->sub.nerows(), s));
+    HIP_OK(hipMemsetAsync(gs.zP.p, 0, sizeof(double) * c->sub.nerows(), s));
     HIP_OK(hipMemsetAsync(gs.colv_own.p, 0, sizeof(double) * c->n * c->m, s));
     int rc = 0;
     for (int part = 0; part < 4 && !rc; part++) {
@@ -1519,11 +1519,11 @@ int gs_apply_c(iemic_ctx* c, const double* rc, double* z, bool staged) { return 
 static int gs_apply_impl(iemic_ctx* c, const double* r, double* z, bool cmp, bool staged)
 {
     BlockGS& gs = c->gs;
-    const Lay L = lay_of(c);
-    const unsigned gc = (unsigned)((c->nloc + 255) / 256);
+    const Lay L = lay_of(c->sub);
+    const unsigned gc = (unsigned)((c->sub.nloc + 255) / 256);
     hipStream_t s = c->stream;
-    const bool band = c->nranks > 1;
-    const int64_t ps = c->next;
+    const bool band = c->sub.nranks > 1;
+    const int64_t ps = c->sub.next;
     double* zP = gs.zP.p;
     int rc = gs_refresh(c);
     if (rc) return rc;
@@ -1541,7 +1541,7 @@ static int gs_apply_impl(iemic_ctx* c, const double* r, double* z, bool cmp, boo
     /* latitude bands: the last pass also updated the iterate's south halo row U/V (k_gs_uvp),
      * all the T/S right-hand side reads of it beyond the band (A_TS,D couples U/V at j - 1 and
      * W in the column): no exchange (the fixed-step passes only) */
-    const bool ts_local = band && c->npx == 1 && gs.ts_mg > 0 && !gs.dyn_mr && ts_at == gs.dyn_iters &&
+    const bool ts_local = band && c->sub.npx == 1 && gs.ts_mg > 0 && !gs.dyn_mr && ts_at == gs.dyn_iters &&
                           gs.dyn_iters > 1;
     auto ts = [&]() -> int {
         if (band && !ts_local && (ts_at < gs.dyn_iters || gs.dyn_iters > 1)) {
@@ -1584,7 +1584,7 @@ static int gs_apply_impl(iemic_ctx* c, const double* r, double* z, bool cmp, boo
     }
     /* latitude bands: the defect on the two halo rows too (from a 2-deep halo of the U/V/W/P
      * planes), so that the pass needs no exchange of it (2 -> 1 exchange batch per pass) */
-    const bool dhalo = band && c->npx == 1 && gs.act.dvh.p;
+    const bool dhalo = band && c->sub.npx == 1 && gs.act.dvh.p;
     for (int it = 1; !gs.dyn_mr && it < gs.dyn_iters; it++) {
         const bool last = it + 1 == gs.dyn_iters;
         if (band && (rc = dhalo ? halo_exchange_planar(c, zP, 4, ps, 2) : halo_exchange_planar(c, zP, NUN, ps, 1)))

@@ -378,16 +378,16 @@ int spmv_dyn_defect(iemic_ctx* c, const double* z, const double* r, const uint8_
 {
     const BlockGS& gs = c->gs;
     const bool al = gs.act.act.p && gs.act.nact > 0;
-    const int64_t nown = al ? gs.act.nact : c->nloc;
+    const int64_t nown = al ? gs.act.nact : c->sub.nloc;
     const int nblk = (int)((nown + 63) / 64);
-    const int64_t row = (int64_t)c->l * c->nx;
+    const int64_t row = (int64_t)c->l * c->sub.nx;
     const bool hv = halo && gs.act.dvh.p;
     const int nhb = hv ? (int)((2 * row + 63) / 64) : 0;
     const unsigned grid = 8u * (unsigned)((nblk + nhb + 7) / 8);
-    hipLaunchKernelGGL(k_spmv_dyn, dim3(grid), dim3(256), 0, c->stream, sub_lay(c), gs.act.vp, z, r, knP, d,
-                       c->nloc, nblk, (int64_t)c->next, hv ? gs.act.dvh.p : nullptr, nhb,
-                       hv && c->nb[2] >= 0 ? 1 : 0, hv && c->nb[3] >= 0 ? 1 : 0, al ? gs.act.act.p : nullptr, nown,
-                       al && gs.act.dvb.p ? gs.act.dvb.p : nullptr);
+    hipLaunchKernelGGL(k_spmv_dyn, dim3(grid), dim3(256), 0, c->stream, sub_lay(c->sub), gs.act.vp, z, r, knP, d,
+                       c->sub.nloc, nblk, (int64_t)c->sub.next, hv ? gs.act.dvh.p : nullptr, nhb,
+                       hv && c->sub.nb[2] >= 0 ? 1 : 0, hv && c->sub.nb[3] >= 0 ? 1 : 0,
+                       al ? gs.act.act.p : nullptr, nown, al && gs.act.dvb.p ? gs.act.dvb.p : nullptr);
     return 0;
 }
 
@@ -400,14 +400,14 @@ int spmv_kernel(iemic_ctx* c, const double* x, double* y)
         return IEMIC_ESTATE;
     }
     hipStream_t s = c->stream;
-    if (c->nloc >= INT32_MAX) {
+    if (c->sub.nloc >= INT32_MAX) {
         set_error("spmv: more than 2^31 cells per rank");
         return IEMIC_EINVAL;
     }
-    const int tpr = (c->nx + SP7_T - 1) / SP7_T;
-    const int ntile = (int)(c->nloc / c->nx) * tpr;
+    const int tpr = (c->sub.nx + SP7_T - 1) / SP7_T;
+    const int ntile = (int)(c->sub.nloc / c->sub.nx) * tpr;
     const unsigned grid = 8u * (unsigned)((ntile + 7) / 8);
-    hipLaunchKernelGGL(k_spmv7, dim3(grid), dim3(256), 0, s, sub_lay(c), c->d_val.p, x, y, (int)c->nloc, ntile,
+    hipLaunchKernelGGL(k_spmv7, dim3(grid), dim3(256), 0, s, sub_lay(c->sub), c->d_val.p, x, y, (int)c->sub.nloc, ntile,
                        tpr);
     return spmv_intcond(c, x, c->rowintcon >= 0 ? y + c->rowintcon : nullptr);
 }
@@ -419,9 +419,9 @@ static int spmv_intcond(iemic_ctx* c, const double* x, double* yr)
     hipStream_t s = c->stream;
     if (c->su.rowintcon_ref >= 0) {
         /* dense intcond row: y[rowintcon] = intSign * coeff . x (summed over the ranks) */
-        const int64_t o = NUN * c->own0;
+        const int64_t o = NUN * c->sub.own0;
         hipLaunchKernelGGL(k_mdot, dim3(RED_BLOCKS, 1), dim3(256), 0, s, c->d_intc.p + o, (int64_t)0, 1,
-                           x + o, c->nlrows, c->d_red.p);
+                           x + o, c->sub.nlrows(), c->d_red.p);
         hipLaunchKernelGGL(k_mdot_final, dim3(1), dim3(256), 0, s, c->d_red.p, RED_BLOCKS, 1,
                            c->d_red.p + RED_BLOCKS);
         int rc = allreduce_sum(c, c->d_red.p + RED_BLOCKS, 1);
@@ -444,11 +444,11 @@ int spmv_kernel_c(iemic_ctx* c, const double* x, double* yc, hipEvent_t ev0, hip
         return IEMIC_ESTATE;
     }
     hipStream_t s = c->stream;
-    const int tpr = (c->nx + SP7_T - 1) / SP7_T;
+    const int tpr = (c->sub.nx + SP7_T - 1) / SP7_T;
     const unsigned grid = 8u * (unsigned)((gs.act.natile + 7) / 8);
     if (gs.act.natile > 0)
-        hipExtLaunchKernelGGL(k_spmv7c, dim3(grid), dim3(256), 0, s, ev0, ev1, 0, sub_lay(c), (const double*)gs.act.spc.p,
-                              x, yc, (const int4*)gs.act.atl.p, gs.act.natile, tpr);
+        hipExtLaunchKernelGGL(k_spmv7c, dim3(grid), dim3(256), 0, s, ev0, ev1, 0, sub_lay(c->sub),
+                              (const double*)gs.act.spc.p, x, yc, (const int4*)gs.act.atl.p, gs.act.natile, tpr);
     double* yr = nullptr;
     if (c->rowintcon >= 0) {
         if (c->gs.act.ric < 0) {

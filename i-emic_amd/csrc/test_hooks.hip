@@ -76,7 +76,7 @@ extern "C" int iemic_test_cr_solve(iemic_ctx* c, int n, int m, int periodic, int
                                    int nsolve, const double* b, double* x, double* xT, int* info, int* plan)
 {
     if (!c || !info || !plan) return bad("null argument");
-    if (c->nranks != 1) return bad("a single-rank context is needed");
+    if (c->sub.nranks != 1) return bad("a single-rank context is needed");
     if (n < 1 || m < 1 || nsolve < 0 || (int64_t)n * m > (1 << 24)) return bad("cyclic reduction shape out of range");
     if (D ? (!L || !R) : (!S9 || !col_of_ij)) return bad("neither blocks nor 9-point rows");
     if (nsolve && (!b || !x)) return bad("null right-hand side or solution");
@@ -112,7 +112,7 @@ extern "C" int iemic_test_cr_refactor(iemic_ctx* c, int n, int m, int periodic, 
                                       const double* R2, const double* b, double* x)
 {
     if (!c || !D1 || !L1 || !R1 || !D2 || !L2 || !R2 || !b || !x) return bad("null argument");
-    if (c->nranks != 1) return bad("a single-rank context is needed");
+    if (c->sub.nranks != 1) return bad("a single-rank context is needed");
     if (n < 1 || m < 1 || (int64_t)n * m > (1 << 24)) return bad("cyclic reduction shape out of range");
     int rc;
     SchurCR cr;

@@ -806,9 +806,9 @@ static TsLev mg_view(iemic_ctx* c, int q)
      * that all subdomains relax the same colour in the same launch and a cell's neighbours
      * across a cut have the other colour; the x wrap only with one x part */
     const int qc = gs.mg.nlev - 1;
-    V.periodic = c->cfg.periodic && c->npx == 1;
-    V.hj = (q == 0 && c->npy > 1) ? (gs.mg.hr ? 2 : 1) : 0;
-    V.hi = (q < qc && q <= MG_XHALO_LEVELS && c->npx > 1) ? 1 : 0;
+    V.periodic = c->cfg.periodic && c->sub.npx == 1;
+    V.hj = (q == 0 && c->sub.npy > 1) ? (gs.mg.hr ? 2 : 1) : 0;
+    V.hi = (q < qc && q <= MG_XHALO_LEVELS && c->sub.npx > 1) ? 1 : 0;
     V.vis = V.hj;
     V.visi = V.hi;
     V.jpar = gs.mg.par[q];
@@ -876,12 +876,13 @@ struct MgGlob {
 static int mg_global_grid(iemic_ctx* c, MgGlob& G)
 {
     BlockGS& gs = c->gs;
-    const int P = c->nranks, l = c->l, qc = gs.mg.nlev - 1;
+    const Sub& S = c->sub;
+    const int P = S.nranks, l = c->l, qc = gs.mg.nlev - 1;
     int rc;
     /* coarsest columns / rows of every rank: offsets of its rank column / row */
     std::vector<double> dims(2 * P, 0.0);
-    dims[2 * c->rank] = gs.mg.n[qc];
-    dims[2 * c->rank + 1] = gs.mg.m[qc];
+    dims[2 * S.rank] = gs.mg.n[qc];
+    dims[2 * S.rank + 1] = gs.mg.m[qc];
     {
         DevBuf<double> rb;
         if (rb.alloc(2 * P)) return IEMIC_ENOMEM;
@@ -889,14 +890,14 @@ static int mg_global_grid(iemic_ctx* c, MgGlob& G)
         if ((rc = allreduce_sum(c, rb.p, 2 * P))) return rc;
         if ((rc = d2h(c, dims.data(), rb.p, sizeof(double) * 2 * P))) return rc;
     }
-    G.ioff.assign(c->npx + 1, 0);
-    G.joff.assign(c->npy + 1, 0);
-    for (int px = 0; px < c->npx; px++) G.ioff[px + 1] = G.ioff[px] + (int)dims[2 * px];
-    for (int py = 0; py < c->npy; py++) G.joff[py + 1] = G.joff[py] + (int)dims[2 * (py * c->npx) + 1];
-    G.GX = G.ioff[c->npx];
-    G.GY = G.joff[c->npy];
-    G.I0 = G.ioff[c->px];
-    G.J0 = G.joff[c->py];
+    G.ioff.assign(S.npx + 1, 0);
+    G.joff.assign(S.npy + 1, 0);
+    for (int px = 0; px < S.npx; px++) G.ioff[px + 1] = G.ioff[px] + (int)dims[2 * px];
+    for (int py = 0; py < S.npy; py++) G.joff[py + 1] = G.joff[py] + (int)dims[2 * (py * S.npx) + 1];
+    G.GX = G.ioff[S.npx];
+    G.GY = G.joff[S.npy];
+    G.I0 = G.ioff[S.px];
+    G.J0 = G.joff[S.py];
     G.NG = 2 * G.GX * G.GY * l;
     G.bl = 2 * l * G.GX + 1;
     G.bu = G.bl;
@@ -910,7 +911,7 @@ static int mg_global_rows(iemic_ctx* c, const MgGlob& G, const std::vector<doubl
 {
     BlockGS& gs = c->gs;
     const int l = c->l, qc = gs.mg.nlev - 1;
-    const int nc = gs.mg.n[qc], cm = gs.mg.m[qc], mb = c->jb1 - c->jb0;
+    const int nc = gs.mg.n[qc], cm = gs.mg.m[qc], mb = c->sub.mb;
     const int64_t ncl = (int64_t)nc * cm * l;
     int rc;
     H.assign((size_t)G.NG * G.W, 0.0);
@@ -924,7 +925,7 @@ static int mg_global_rows(iemic_ctx* c, const MgGlob& G, const std::vector<doubl
         return true;
     };
     bool ok = true;
-    const bool lwrap = wrap && c->npx == 1;           /* the local level wraps in x */
+    const bool lwrap = wrap && c->sub.npx == 1;           /* the local level wraps in x */
     for (int64_t t = 0; t < ncl; t++) {
         int i, jl, k;
         mg_decode(t, nc, l, i, jl, k);
@@ -956,14 +957,14 @@ static int mg_global_rows(iemic_ctx* c, const MgGlob& G, const std::vector<doubl
     /* cross-subdomain couplings: level-0 T/S couplings of the first / last latitude row (-j /
      * +j) and the first / last column (-i / +i), summed into the edge aggregates */
     {
-        const int64_t nx = c->nx, slab = (int64_t)l * nx;
+        const int64_t nx = c->sub.nx, slab = (int64_t)l * nx;
         std::vector<double> e((size_t)slab * mb);
         for (int dir = 0; dir < 4; dir++) {
-            if (c->nb[dir] < 0) continue;
+            if (c->sub.nb[dir] < 0) continue;
             const int q = dir == 0 ? 0 : dir == 1 ? 1 : dir == 2 ? 2 : 3;   /* -i, +i, -j, +j */
             for (int R = 0; R < 2; R++) {
                 /* the owned rows of coupling q of row R (ext layout: one slab) */
-                const double* src = gs.sw.tsoff.p + (int64_t)(R * 8 + q) * c->next + c->own0;
+                const double* src = gs.sw.tsoff.p + (int64_t)(R * 8 + q) * c->sub.next + c->sub.own0;
                 if ((rc = d2h(c, e.data(), src, sizeof(double) * e.size()))) return rc;
                 for (int jl = 0; jl < mb; jl++)
                     for (int k = 0; k < l; k++)
@@ -973,8 +974,8 @@ static int mg_global_rows(iemic_ctx* c, const MgGlob& G, const std::vector<doubl
                             const double v = e[((int64_t)jl * l + k) * nx + il];
                             if (v == 0.0) continue;
                             const int Is = G.I0 + (il >> qc), Js = G.J0 + (jl >> qc);
-                            const int Id = dir == 0 ? gwrap(G.I0 - 1) : dir == 1 ? gwrap(G.ioff[c->px + 1]) : Is;
-                            const int Jd = dir == 2 ? G.J0 - 1 : dir == 3 ? G.joff[c->py + 1] : Js;
+                            const int Id = dir == 0 ? gwrap(G.I0 - 1) : dir == 1 ? gwrap(G.ioff[c->sub.px + 1]) : Is;
+                            const int Jd = dir == 2 ? G.J0 - 1 : dir == 3 ? G.joff[c->sub.py + 1] : Js;
                             ok &= add(gidx(Js, Is, k, R), gidx(Jd, Id, k, R), v);
                         }
             }
@@ -1007,7 +1008,7 @@ static int mg_global_setup(iemic_ctx* c, const std::vector<double>& off, const s
 {
     BlockGS& gs = c->gs;
     gs.mg.glob = 0;
-    if (c->nranks <= 1 || c->l > 64) return 0;
+    if (c->sub.nranks <= 1 || c->l > 64) return 0;
     int rc;
     MgGlob G;
     if ((rc = mg_global_grid(c, G))) return rc;
@@ -1191,12 +1192,12 @@ static int mg_levels(iemic_ctx* c)
     const int l = c->l;
     int rc;
     /* latitude bands, one sweep: level 0 keeps 2 halo rows (mg_vcycle) */
-    gs.mg.hr = c->npy > 1 && c->npx == 1 && std::max(1, gs.mg.sweeps) == 1;
+    gs.mg.hr = c->sub.npy > 1 && c->sub.npx == 1 && std::max(1, gs.mg.sweeps) == 1;
     /* coarsen 2x2 horizontally until the level has <= 128 cells (<= 256 unknowns); the
      * number of levels is that of the largest subdomain, the same on every rank, so the
      * coarsest grids of the ranks tile the global coarsest problem */
-    int N = (c->n + c->npx - 1) / c->npx, M = (c->m + c->npy - 1) / c->npy, q = 0;
-    int n = c->nx, m = c->jb1 - c->jb0;
+    int N = (c->n + c->sub.npx - 1) / c->sub.npx, M = (c->m + c->sub.npy - 1) / c->sub.npy, q = 0;
+    int n = c->sub.nx, m = c->sub.mb;
     gs.mg.n[0] = n;
     gs.mg.m[0] = m;
     gs.mg.crd = 0;
@@ -1205,7 +1206,7 @@ static int mg_levels(iemic_ctx* c)
      * longitudes): an exact coarse solve, one GEMV per V-cycle instead of the last
      * levels' ~9 latency-bound launches */
     auto cr_ok = [&](int nn, int mm) {
-        return c->nranks == 1 && (int64_t)nn * mm * l <= TsMg::CR_CELLS && 2 * mm * l <= 192 && nn >= 2;
+        return c->sub.nranks == 1 && (int64_t)nn * mm * l <= TsMg::CR_CELLS && 2 * mm * l <= 192 && nn >= 2;
     };
     while (q + 1 < TsMg::MAX && (q == 0 || (int64_t)N * M * l > 128) && (N > 1 || M > 1) &&
            !(q > 0 && cr_ok(n, m))) {
@@ -1236,12 +1237,12 @@ static int mg_levels(iemic_ctx* c)
             return v;
         };
         int io = 0, jo = 0, off, cnt;
-        for (int px = 0; px < c->px; px++) {
-            part_of(c->n, c->npx, px, off, cnt);
+        for (int px = 0; px < c->sub.px; px++) {
+            part_of(c->n, c->sub.npx, px, off, cnt);
             io += coarse(cnt);
         }
-        for (int py = 0; py < c->py; py++) {
-            part_of(c->m, c->npy, py, off, cnt);
+        for (int py = 0; py < c->sub.py; py++) {
+            part_of(c->m, c->sub.npy, py, off, cnt);
             jo += coarse(cnt);
         }
         gs.mg.par[lv] = (io + jo) & 1;
@@ -1269,8 +1270,8 @@ static int mg_operators(iemic_ctx* c)
     int rc;
     {
         const TsLev V0 = mg_view(c, 0);
-        hipLaunchKernelGGL(k_mg_pack0, dim3(blocks_for(c->nloc)), dim3(256), 0, s, gs.sw.tsoff.p, gs.tsdiag.p,
-                           lay_of(c), c->next, V0, gs.mg.off[0].p, gs.mg.diag[0].p);
+        hipLaunchKernelGGL(k_mg_pack0, dim3(blocks_for(c->sub.nloc)), dim3(256), 0, s, gs.sw.tsoff.p, gs.tsdiag.p,
+                           lay_of(c->sub), c->sub.next, V0, gs.mg.off[0].p, gs.mg.diag[0].p);
     }
     for (int q = 1; q < gs.mg.nlev; q++) {
         TsLev F = mg_view(c, q - 1);
@@ -1293,7 +1294,7 @@ static int mg_operators(iemic_ctx* c)
          * halo-row line solves of mg_vcycle) */
         const TsLev V = mg_view(c, 0);
         const int64_t RW = (int64_t)V.n * V.l;
-        const int so = c->nb[2], no = c->nb[3];
+        const int so = c->sub.nb[2], no = c->sub.nb[3];
         std::vector<Msg> y;
         double* const arr[3] = {gs.mg.off[0].p, gs.mg.diag[0].p, gs.mg.fac[0].p};
         const int ncomp[3] = {16, 4, 12};
@@ -1352,7 +1353,7 @@ static int mg_coarse_dev(iemic_ctx* c, int qc, int64_t ncl, int N)
     HIP_OK(hipMemsetAsync(gs.mg.cinfo.p, 0, sizeof(int), s));
     hipLaunchKernelGGL(k_mg_coarse_dense, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, s,
                        (const double*)gs.mg.off[qc].p, (const double*)gs.mg.diag[qc].p, ncl,
-                       gs.mg.n[qc], gs.mg.m[qc], l, c->cfg.periodic && c->npx == 1, A.p);
+                       gs.mg.n[qc], gs.mg.m[qc], l, c->cfg.periodic && c->sub.npx == 1, A.p);
     /* k_cr_inv reads column-major: it inverts A^T and writes the result column-major,
      * which is A^-1 row-major -- the layout k_gemv applies */
     if ((rc = cr_inverse_dev(s, N, A.p, gs.mg.cinv.p, gs.mg.cinfo.p))) return rc;
@@ -1398,7 +1399,7 @@ static int mg_coarse_host(iemic_ctx* c, int qc, int64_t ncl, int N)
                 }
                 if (jj < 0 || jj >= cm || kk < 0 || kk >= l) continue;
                 if (ii < 0 || ii >= cn) {
-                    if (!(c->cfg.periodic && c->npx == 1)) continue;
+                    if (!(c->cfg.periodic && c->sub.npx == 1)) continue;
                     ii = (ii + cn) % cn;
                 }
                 const int64_t nb = ((int64_t)jj * cn + ii) * l + kk;
@@ -1432,7 +1433,7 @@ int ts_mg_setup(iemic_ctx* c, int sweeps)
     const int64_t ncl = (int64_t)gs.mg.n[qc] * gs.mg.m[qc] * c->l;
     const int N = (int)(2 * ncl);
     if (gs.mg.crd) return mg_coarse_cr(c, qc, ncl, N);
-    if (N <= 192 && c->nranks <= 1) return mg_coarse_dev(c, qc, ncl, N);
+    if (N <= 192 && c->sub.nranks <= 1) return mg_coarse_dev(c, qc, ncl, N);
     return mg_coarse_host(c, qc, ncl, N);
 }
 
@@ -1442,7 +1443,7 @@ static int mg_halo(iemic_ctx* c, const TsLev& V)
 {
     if (!V.vis && !V.visi) return 0;
     const int64_t W = V.n + 2 * V.hi, L = V.l;
-    const int w = c->nb[0], e = c->nb[1], so = c->nb[2], no = c->nb[3];
+    const int w = c->sub.nb[0], e = c->sub.nb[1], so = c->sub.nb[2], no = c->sub.nb[3];
     std::vector<Msg> x, y;
     for (double* z : {V.z, V.z + V.cstr}) {
         if (V.visi) {
@@ -1470,7 +1471,7 @@ static int mg_halo(iemic_ctx* c, const TsLev& V)
 static int mg_halo2(iemic_ctx* c, const TsLev& V, bool with_b)
 {
     const int64_t RW = (int64_t)V.n * V.l;
-    const int so = c->nb[2], no = c->nb[3];
+    const int so = c->sub.nb[2], no = c->sub.nb[3];
     std::vector<Msg> y;
     for (double* z : {V.z, V.z + V.cstr}) {
         auto rows = [&](int jl) { return Seg{z, (V.hj + jl) * RW, 1, 2 * RW, 2 * RW}; };
@@ -1592,7 +1593,7 @@ static int mg_vcycle(iemic_ctx* c, int q, bool first, double* zout)
      * (the neighbour's own lines, operation for operation), so that the restriction and the
      * last colour-0 launch read them without another exchange (4 -> 2 batches per V-cycle) */
     const bool hrel = q == 0 && gs.mg.hr && V.hj == 2 && nu == 1 && nc == 2 && first;
-    const int hr = hrel ? ((c->nb[2] >= 0 ? 1 : 0) | (c->nb[3] >= 0 ? 2 : 0)) : 0;
+    const int hr = hrel ? ((c->sub.nb[2] >= 0 ? 1 : 0) | (c->sub.nb[3] >= 0 ? 2 : 0)) : 0;
     for (int sw = 0; sw < nu; sw++)
         for (int h = (sw == 0 && first) ? 1 : 0; h < nc; h++) {
             if ((rc = hrel ? mg_halo2(c, V, true) : mg_halo(c, V))) return rc;
@@ -1644,10 +1645,10 @@ static int mg_vcycle(iemic_ctx* c, int q, bool first, double* zout)
 int ts_mg_solve(iemic_ctx* c, const double* zd, double* z, bool out, bool side)
 {
     BlockGS& gs = c->gs;
-    const Lay L = lay_of(c);
+    const Lay L = lay_of(c->sub);
     hipStream_t s = c->stream;
     const TsLev V0 = mg_view(c, 0);
-    const unsigned ge = (unsigned)(((c->nx + MG_TI - 1) / MG_TI) * V0.mb);
+    const unsigned ge = (unsigned)(((c->sub.nx + MG_TI - 1) / MG_TI) * V0.mb);
     with_lanes(mg_lanes(c->l), [&](auto p) {
         hipLaunchKernelGGL(k_mg_entry<LANES_OF(p)>, dim3(ge), dim3(256), 0, s, gs.act.vp, gs.knP.p, gs.kmask.p,
                            gs.rrP.p, zd, L, V0);

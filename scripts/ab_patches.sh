@@ -118,7 +118,7 @@ old='''                hipLaunchKernelGGL(k_mdot_final, dim3(2 * nv + 3), dim3(2
                 if ((rc2 = allreduce_sum(c, c->d_hbuf.p, 2 * nv + 3))) return rc2;
                 hipLaunchKernelGGL(k_dcgs_coef, dim3(1), dim3(256), 0, c->stream, c->d_hbuf.p, nv,
                                    c->d_hbuf.p + RED_ROWS);'''
-new2='''                if (c->nranks <= 1) {
+new2='''                if (c->sub.nranks <= 1) {
                     hipLaunchKernelGGL(k_dcgs_final_coef, dim3(1), dim3(1024), 0, c->stream, c->d_part.p, nbx1,
                                        c->d_hbuf.p, nv, c->d_hbuf.p + RED_ROWS);
                 } else {
@@ -335,10 +335,10 @@ new='''__global__ void __launch_bounds__(256) k_spmv_dyn(SubLay X, const double*
 
 '''
 s=s[:a]+new+s[b:]
-old="""    const int nblk = (int)((c->nloc + 63) / 64);
+old="""    const int nblk = (int)((c->sub.nloc + 63) / 64);
     const unsigned grid = 8u * (unsigned)((nblk + 7) / 8);
     hipLaunchKernelGGL(k_spmv_dyn,"""
-new2="""    const int nblk = (int)((c->nloc + 127) / 128);
+new2="""    const int nblk = (int)((c->sub.nloc + 127) / 128);
     const unsigned grid = 8u * (unsigned)((nblk + 7) / 8);
     hipLaunchKernelGGL(k_spmv_dyn,"""
 assert old in s

@@ -16,8 +16,7 @@
 using namespace iemic;
 
 struct Emul {
-    host::Setup su;
-    Sub sub;
+    host::Setup su;                /* also the subdomain record (decomp.h Sub) */
     std::vector<double> frc, qcor, val;
     std::vector<double> atm;      /* coupled: tatm | qatm | albe (n*m each) */
     const double* atm_p() const { return atm.empty() ? nullptr : atm.data(); }
@@ -72,9 +71,7 @@ void* emul_create_sub(const iemic_grid* grid, const int* landm, int rank, int nr
     Sub d;
     if (sub_init(d, grid->n, grid->m, grid->l, grid->periodic, rank, nranks, npx)) return nullptr;
     Emul* e = new Emul();
-    e->sub = d;
-    const int s0[2] = {d.ib0, d.jb0}, s1[2] = {d.ib1, d.jb1};
-    e->su.init(*grid, landm, s0, s1, d.npx > 1 ? 1 : 0);
+    e->su.init(*grid, landm, d);
     e->su.vmix_init();
     e->atm.assign((size_t)4 * e->su.n * e->su.m, 0.0);
     return e;
@@ -82,16 +79,26 @@ void* emul_create_sub(const iemic_grid* grid, const int* landm, int rank, int nr
 /* subdomain facts: ib0 ib1 jb0 jb1 npx npy nb[4] */
 void emul_sub_info(void* h, int* out10)
 {
-    const Sub& d = ((Emul*)h)->sub;
+    const Sub& d = ((Emul*)h)->su;
     const int v[10] = {d.ib0, d.ib1, d.jb0, d.jb1, d.npx, d.npy, d.nb[0], d.nb[1], d.nb[2], d.nb[3]};
     for (int q = 0; q < 10; q++) out10[q] = v[q];
+}
+/* the whole record: n m l periodic | rank nranks npx npy px py | ib0 ib1 jb0 jb1 nx mb hx |
+ * xb nloc next own0 | nb[4] | nlrows nerows (27 values) */
+void emul_sub_layout(void* h, int64_t* out)
+{
+    const Sub& d = ((Emul*)h)->su;
+    const int64_t v[27] = {d.n, d.m, d.l, d.periodic, d.rank, d.nranks, d.npx, d.npy, d.px, d.py,
+                           d.ib0, d.ib1, d.jb0, d.jb1, d.nx, d.mb, d.hx, d.xb, d.nloc, d.next, d.own0,
+                           d.nb[0], d.nb[1], d.nb[2], d.nb[3], d.nlrows(), d.nerows()};
+    for (int q = 0; q < 27; q++) out[q] = v[q];
 }
 /* the library's exchange plan (decomp.h plan_ext): phase 0 (x) or 1 (y); up to cap
  * messages as (send, peer, off, nblk, len, stride); returns the message count */
 int emul_plan(void* h, int width, int depth, int phase, int64_t* out, int cap)
 {
     std::vector<MsgD> x, y;
-    plan_ext(((Emul*)h)->sub, width, depth, x, y);
+    plan_ext(((Emul*)h)->su, width, depth, x, y);
     const std::vector<MsgD>& v = phase == 0 ? x : y;
     for (size_t q = 0; q < v.size() && (int)q < cap; q++) {
         const int64_t r[6] = {v[q].send, v[q].peer, v[q].s.off, v[q].s.nblk, v[q].s.len, v[q].s.stride};
@@ -130,7 +137,7 @@ void emul_destroy(void* h) { delete (Emul*)h; }
 void emul_set_par(void* h, int idx, double v) { ((Emul*)h)->su.par[idx] = v; }
 double emul_get_par(void* h, int idx) { return ((Emul*)h)->su.par[idx]; }
 /* ext length (rows) of the band */
-int64_t emul_ext_rows(void* h) { return NUN * ((Emul*)h)->su.next; }
+int64_t emul_ext_rows(void* h) { return ((Emul*)h)->su.nerows(); }
 
 static void forcing(Emul* e)
 {
@@ -139,7 +146,7 @@ static void forcing(Emul* e)
     std::vector<double> ft = su.forcing_tables();
     e->qcor.assign(8, 0.0);
     forcing_qint(g, ft.data(), e->qcor.data(), su.cfg.tres == 0, su.cfg.sres == 0);
-    e->frc.assign((size_t)NUN * su.next, 0.0);
+    e->frc.assign((size_t)su.nerows(), 0.0);
     for (int64_t lc = 0; lc < su.nloc; lc++) {
         int i, j, k;
         owned_cell(g, lc, i, j, k);
@@ -154,7 +161,7 @@ static void mix_control(Emul* e, const double* x)
     if (su.cfg.vmix != 2 || su.vmix_fix) return;
     double st = 0.0, ss = 0.0;
     for (int64_t lc = 0; lc < su.nloc; lc++) {
-        const int64_t r = NUN * ((int64_t)HALO * su.l * su.nx + lc);
+        const int64_t r = NUN * (su.own0 + lc);
         st += x[r + TT] * x[r + TT];
         ss += x[r + SS] * x[r + SS];
     }

@@ -63,6 +63,36 @@ def mask_fix(orc, cfg, L, max_fix: int = 5):
     return L
 
 
+SUB_FIELDS = ("n m l periodic rank nranks npx npy px py ib0 ib1 jb0 jb1 nx mb hx xb nloc next own0 "
+              "nbW nbE nbS nbN nlrows nerows").split()
+
+
+def sub_layout_formulas(n, m, l, periodic, rank, nranks, npx, npy):
+    """The subdomain record of rank `rank` on an npx x npy process grid, from the layout
+    comment in stencil.h and the partition rule of TRIOS_Domain.C:151-162 (the first N % np
+    parts take one more), restated here; keys as SUB_FIELDS."""
+    halo = 2
+
+    def part_of(N, parts, p):
+        return p * (N // parts) + min(p, N % parts), N // parts + (1 if p < N % parts else 0)
+
+    px, py = rank % npx, rank // npx
+    ib0, nx = part_of(n, npx, px)
+    jb0, mb = part_of(m, npy, py)
+    hx = halo if npx > 1 else 0
+    xb = nx * l * (mb + 2 * halo)
+    nxt = xb + 2 * hx * l * (mb + 2 * halo)
+    nloc = nx * l * mb
+    wrap = bool(periodic) and npx > 1
+    nbW = rank - 1 if px > 0 else (rank + npx - 1 if wrap else -1)
+    nbE = rank + 1 if px < npx - 1 else (rank - (npx - 1) if wrap else -1)
+    nbS = rank - npx if py > 0 else -1
+    nbN = rank + npx if py < npy - 1 else -1
+    v = (n, m, l, int(periodic), rank, nranks, npx, npy, px, py, ib0, ib0 + nx, jb0, jb0 + mb, nx, mb, hx,
+         xb, nloc, nxt, halo * l * nx, nbW, nbE, nbS, nbN, 6 * nloc, 6 * nxt)
+    return dict(zip(SUB_FIELDS, v))
+
+
 def emul_lib():
     """the CPU emulation library of the device assembly (tests/emul)"""
     return C.CDLL(EMUL_LIB)
@@ -111,6 +141,13 @@ class Emul:
         for idx, v in cfg.par_list():
             lib.emul_set_par(self.h, idx, v)
         self.ext_rows = lib.emul_ext_rows(self.h)
+
+    def sub_layout(self) -> dict:
+        """the library's subdomain record (decomp.h Sub), keys as SUB_FIELDS"""
+        out = np.zeros(len(SUB_FIELDS), dtype=np.int64)
+        self.lib.emul_sub_layout.argtypes = [C.c_void_p, P(C.c_int64)]
+        self.lib.emul_sub_layout(self.h, _lib.ptr(out, C.c_int64))
+        return dict(zip(SUB_FIELDS, (int(v) for v in out)))
 
     def plan(self, width: int, depth: int, phase: int):
         """the library's halo-exchange plan: [(send, peer, off, nblk, len, stride)]"""

@@ -152,3 +152,54 @@ def test_decomp2d_matches_reference_rule(emul):
             assert e.nb[0] == (r - 1 if px > 0 else (r + e.npx - 1 if e.npx > 1 else -1))
             assert e.nb[3] == (r + e.npx if py < e.npy - 1 else -1)
         assert (seen == 1).all()
+
+
+# (n, m, l, periodic, nranks, npx)
+RECORD_CASES = [
+    (6, 6, 4, 0, 1, 1),          # one rank
+    (8, 8, 4, 1, 2, 1),          # bands
+    (16, 16, 16, 1, 3, 1),       # uneven rows
+    (16, 16, 16, 1, 4, 2),       # x split, periodic
+    (9, 7, 3, 0, 4, 2),          # both remainders, not periodic
+    (96, 38, 12, 1, 8, 0),       # the reference rule's 4 x 2
+]
+
+
+def _bare(n, m, l, periodic):
+    """a configuration and an all-ocean mask of the given size: the record depends on neither"""
+    from iemic import config as cf
+    return cf.THCMConfig(n=n, m=m, l=l, periodic=bool(periodic)), np.zeros((l + 2, m + 2, n + 2), dtype=np.int32)
+
+
+@pytest.mark.parametrize("n,m,l,periodic,nranks,npx", RECORD_CASES)
+def test_subdomain_record_matches_layout_formulas(emul, n, m, l, periodic, nranks, npx):
+    """decomp.h's Sub, the one host statement of the subdomain, as Setup holds it: every field
+    of every rank equals the formulas of stencil.h's layout comment (helpers.sub_layout_formulas);
+    the owned ranges tile the grid exactly once and the neighbour relation is mutual."""
+    from helpers import Emul, sub_layout_formulas
+    c, L = _bare(n, m, l, periodic)
+    recs = [Emul(c, L, sub=(r, nranks, npx)).sub_layout() for r in range(nranks)]
+    gx, gy = recs[0]["npx"], recs[0]["npy"]
+    if npx > 0:
+        assert (gx, gy) == (npx, nranks // npx)
+    else:
+        assert (gx, gy) == (4, 2)
+    seen = np.zeros((m, n), dtype=int)
+    for r, rec in enumerate(recs):
+        assert rec == sub_layout_formulas(n, m, l, periodic, r, nranks, gx, gy), r
+        seen[rec["jb0"]:rec["jb1"], rec["ib0"]:rec["ib1"]] += 1
+    assert (seen == 1).all()
+    for a, ra in enumerate(recs):
+        for b, rb in enumerate(recs):
+            assert (ra["nbE"] == b) == (rb["nbW"] == a), (a, b)
+            assert (ra["nbN"] == b) == (rb["nbS"] == a), (a, b)
+
+
+def test_subdomain_record_refuses_self_wrapping_halo(emul):
+    """7 columns over 2 x parts on a periodic grid: the wider part (4) plus both x halos (2 HALO)
+    exceeds n, so the halo would wrap onto the part's own columns"""
+    from helpers import Emul
+    c, L = _bare(7, 5, 3, 1)
+    for r in range(2):
+        with pytest.raises(ValueError):
+            Emul(c, L, sub=(r, 2, 2))

@@ -139,6 +139,28 @@ def test_subdomains_global2_newton_mixing(oracle_lib, nranks, npx, schur_passes)
     assert lin <= 2e-8, lin
 
 
+def test_subdomain_layout_matches_formulas():
+    """gateway16 on 2 x 2 in-process ranks: each context's iemic_layout equals the formulas of
+    stencil.h's layout comment (helpers.sub_layout_formulas).  Creation only."""
+    from helpers import sub_layout_formulas
+    from iemic.ocean import Ocean
+    c = cf.preset("gateway16", mixing=0)
+    L0 = golden_landm("gateway16")
+    nranks, npx = 4, 2
+
+    def fn(r, group):
+        oc = Ocean(c, landm=L0, local_group=group, rank=r, nranks=nranks, npx=npx)
+        lay = oc.layout()
+        oc.close()
+        return lay
+
+    for r, lay in enumerate(_run_bands(nranks, fn)):
+        w = sub_layout_formulas(c.n, c.m, c.l, c.periodic, r, nranks, npx, nranks // npx)
+        assert lay == dict(ext_rows=w["nerows"], own_first=6 * w["own0"], own_rows=w["nlrows"],
+                           jb0=w["jb0"], jb1=w["jb1"], rank=r, nranks=nranks, ib0=w["ib0"], ib1=w["ib1"],
+                           npx=npx, npy=nranks // npx, hx=w["hx"]), r
+
+
 def _run_bands(nranks, fn):
     """Run fn(rank, group) on nranks host threads sharing one in-process group."""
     from iemic import _lib
