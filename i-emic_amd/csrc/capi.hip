@@ -277,6 +277,7 @@ static int create_impl(iemic_ctx** out, const iemic_grid* grid, const int* landm
         const double v = std::atof(e);
         if (v > 0.0) c->comm_timeout_s = v;
     }
+    if (const char* e = std::getenv("IEMIC_SERIAL_SETUP")) c->serial_setup = std::atoi(e) != 0;
     c->cfg = *grid;
     c->device = std::min(std::max(grid->device, 0), ndev - 1);
     if (hipSetDevice(c->device) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
@@ -323,7 +324,7 @@ static int create_impl(iemic_ctx** out, const iemic_grid* grid, const int* landm
     rc |= c->d_red.alloc(2048);
     rc |= c->d_part.alloc((size_t)RED_BLOCKS * RED_ROWS);
     rc |= c->d_hbuf.alloc((size_t)2 * RED_ROWS);
-    /* coherent: k_dcgs_coef writes the Hessenberg rows straight into it */
+    /* coherent: the DCGS2 update (dcgs_rows_out) writes the Hessenberg rows straight into it */
     if (!rc && hipHostMalloc(&c->h_red, sizeof(double) * 2 * RED_ROWS, hipHostMallocCoherent) != hipSuccess) rc = 1;
     if (rc) {
         set_error("iemic_create: out of device memory");

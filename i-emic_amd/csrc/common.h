@@ -335,8 +335,11 @@ struct iemic_ctx {
     iemic_grid cfg;
     int device = 0;
     hipStream_t stream = nullptr;
-    hipStream_t side = nullptr;      /* second stream: the early T/S V-cycles (one rank)  */
+    hipStream_t side = nullptr;      /* second stream (one rank): the early T/S V-cycles,  */
+                                     /* the T/S set-up beside the Schur factorisation      */
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    int serial_setup = 0;            /* IEMIC_SERIAL_SETUP=1 at creation: gs_compute keeps the  */
+                                     /* Schur and T/S set-up chains on one stream            */
     int n = 0, m = 0, l = 0;
     int64_t ncell = 0, nrows = 0;    /* global cells / rows                               */
     int64_t rowintcon = -1;          /* ext row of the integral condition if owned        */

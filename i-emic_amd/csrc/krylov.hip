@@ -246,11 +246,15 @@ __global__ void __launch_bounds__(256) k_dcgs_dot1(const double* __restrict__ V,
 
 /* DCGS2 coefficients on the device (no host round trip before the update pass): from the
  * summed dot rows hb = [Q^T u, Q^T w interleaved | u.u, u.w, w.w], beta = sqrt(u.u - |a|^2),
- * h_jj = (u.w - a.b) / beta, gamma = h_jj / beta; coef = [a | b - gamma a], coef[DCGS_SCAL..] =
- * 1/beta, gamma; beta, h_jj appended to hb (rows 2nv+3, 2nv+4) for the host's Hessenberg
- * column.  A breakdown (beta = 0) gives zero scales; the host stops on it. */
-__global__ void __launch_bounds__(256) k_dcgs_coef(double* __restrict__ hb, int nv, double* __restrict__ coef,
-                                                   double* __restrict__ hrows)
+ * h_jj = (u.w - a.b) / beta, gamma = h_jj / beta; the update's coefficients are a and
+ * b - gamma a, its scales 1/beta and gamma.  A breakdown (beta = 0) gives zero scales; the
+ * host stops on it.  One 256-thread workgroup: the strided partial sums and block_sum_n<2>
+ * fix the summation order, so every workgroup that runs this on the same hb gets the same
+ * bits. */
+struct DcgsScal {
+    double bt, hjj, inv_beta, gamma;
+};
+__device__ __forceinline__ DcgsScal dcgs_scal(const double* __restrict__ hb, int nv)
 {
     __shared__ double sm[2 * 4];
     __shared__ double tot[2];
@@ -271,37 +275,63 @@ __global__ void __launch_bounds__(256) k_dcgs_coef(double* __restrict__ hb, int 
     const bool ok = bt > 0.0 && bt <= 1.79e308;
     const double hjj = ok ? (hb[2 * nv + 1] - tot[1]) / bt : 0.0;
     const double gamma = ok ? hjj / bt : 0.0;
+    return DcgsScal{bt, hjj, ok ? 1.0 / bt : 0.0, gamma};
+}
+/* beta, h_jj appended to hb (rows 2nv+3, 2nv+4) for the host's Hessenberg column, and the
+ * rows straight into its pinned (coherent) slot: no device-to-host copy launch per Arnoldi
+ * step.  One workgroup calls this, all its threads. */
+__device__ __forceinline__ void dcgs_rows_out(double* __restrict__ hb, int nv, const DcgsScal& sc,
+                                              double* __restrict__ hrows)
+{
+    if (threadIdx.x == 0) {
+        hb[2 * nv + 3] = sc.bt;
+        hb[2 * nv + 4] = sc.hjj;
+    }
+    if (hrows) {
+        for (int i = threadIdx.x; i < 2 * nv + 3; i += blockDim.x) hrows[i] = hb[i];
+        if (threadIdx.x == 0) {
+            hrows[2 * nv + 3] = sc.bt;
+            hrows[2 * nv + 4] = sc.hjj;
+        }
+    }
+}
+/* The coefficients as a launch of their own: coef = [a | b - gamma a], coef[DCGS_SCAL..] =
+ * 1/beta, gamma.  The solve runs it only where no update pass follows (the last step of a
+ * full cycle); it is also the reference the fused update is tested against. */
+__global__ void __launch_bounds__(256) k_dcgs_coef(double* __restrict__ hb, int nv, double* __restrict__ coef,
+                                                   double* __restrict__ hrows)
+{
+    const DcgsScal sc = dcgs_scal(hb, nv);
     for (int i = threadIdx.x; i < nv; i += blockDim.x) {
         const double a = hb[2 * i], b = hb[2 * i + 1];
         coef[i] = a;
-        coef[nv + i] = b - a * gamma;
+        coef[nv + i] = b - a * sc.gamma;
     }
     if (threadIdx.x == 0) {
-        coef[DCGS_SCAL] = ok ? 1.0 / bt : 0.0;
-        coef[DCGS_SCAL + 1] = gamma;
-        hb[2 * nv + 3] = bt;
-        hb[2 * nv + 4] = hjj;
+        coef[DCGS_SCAL] = sc.inv_beta;
+        coef[DCGS_SCAL + 1] = sc.gamma;
     }
-    /* the rows for the host's Hessenberg column, straight into its pinned (coherent) slot:
-     * no device-to-host copy launch per Arnoldi step */
-    if (hrows) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < 2 * nv + 5; i += blockDim.x) hrows[i] = hb[i];
-    }
+    dcgs_rows_out(hb, nv, sc, hrows);
 }
 
 /* DCGS2 update pass, one read of Q:  q_j = (u - Q a) * inv_beta,
- * w = (w - Q c - gamma * u) * inv_beta  (coef = [a (nvec) | c (nvec)], inv_beta and gamma at
- * coef[DCGS_SCAL..]); u is overwritten by q_j.  Scaling the next candidate w by the same
- * 1/beta (lagged normalisation) keeps every candidate at the scale of a normalised Arnoldi
- * vector, so its norm never compounds the earlier subdiagonals (no overflow / false breakdown
- * over long cycles). */
+ * w = (w - Q c - gamma * u) * inv_beta; u is overwritten by q_j.  Scaling the next candidate
+ * w by the same 1/beta (lagged normalisation) keeps every candidate at the scale of a
+ * normalised Arnoldi vector, so its norm never compounds the earlier subdiagonals (no
+ * overflow / false breakdown over long cycles). */
+/* FUSED: every workgroup forms a, c, inv_beta and gamma itself from the summed dot rows hb
+ * (dcgs_scal: the bits of k_dcgs_coef, no workgroup depends on another), so no coefficient
+ * launch sits between the dot pass and this one; workgroup 0 writes beta, h_jj and the
+ * host's rows (hb rows 2nv+3.. are read by no workgroup).  !FUSED: hb is the ready
+ * coefficient array of k_dcgs_coef (coef = [a (nvec) | c (nvec)], scales at DCGS_SCAL). */
 /* rrP (the compressed basis with the block GS): the new candidate w -- the next step's
  * preconditioner input -- also goes straight into the block GS's planar right-hand side
  * (rows 2e, 2e + 1 of w are unknowns R, R + 1 of active cell act[2e / 6]), so the apply
  * skips its entry kernel k_gs_rr_c */
+template <bool FUSED>
 __global__ void __launch_bounds__(256) k_dcgs_update(const double* __restrict__ V, int64_t ldv,
-                                                     int nvec, const double* __restrict__ coef,
+                                                     int nvec, double* __restrict__ hb,
+                                                     double* __restrict__ hrows,
                                                      double* __restrict__ u, double* __restrict__ w,
                                                      int64_t N, const int* __restrict__ act = nullptr,
                                                      int64_t own0 = 0, int64_t ps = 0,
@@ -310,9 +340,23 @@ __global__ void __launch_bounds__(256) k_dcgs_update(const double* __restrict__ 
     /* two consecutive elements per lane (16-byte loads; N even), four basis vectors per step */
     constexpr int UN = 4;
     __shared__ double cs[2 * 1024];
-    for (int i = threadIdx.x; i < 2 * nvec; i += blockDim.x) cs[i] = coef[i];
+    double inv_beta, gamma;
+    if (FUSED) {
+        const DcgsScal sc = dcgs_scal(hb, nvec);
+        for (int i = threadIdx.x; i < nvec; i += blockDim.x) {
+            const double a = hb[2 * i], b = hb[2 * i + 1];
+            cs[i] = a;
+            cs[nvec + i] = b - a * sc.gamma;
+        }
+        if (blockIdx.x == 0) dcgs_rows_out(hb, nvec, sc, hrows);
+        inv_beta = sc.inv_beta;
+        gamma = sc.gamma;
+    } else {
+        for (int i = threadIdx.x; i < 2 * nvec; i += blockDim.x) cs[i] = hb[i];
+        inv_beta = hb[DCGS_SCAL];
+        gamma = hb[DCGS_SCAL + 1];
+    }
     __syncthreads();
-    const double inv_beta = coef[DCGS_SCAL], gamma = coef[DCGS_SCAL + 1];
     const double* a = cs;
     const double* cc = cs + nvec;
     const int64_t N2 = N / 2;
@@ -351,6 +395,26 @@ __global__ void __launch_bounds__(256) k_dcgs_update(const double* __restrict__ 
             rrP[cell + (R + 1) * ps] = wn.y;
         }
     }
+}
+
+/* the update pass of one Arnoldi step on the context's stream: fused (the solve), or
+ * k_dcgs_coef and the update from its coefficient array (the test hook's reference).  hb:
+ * the summed dot rows, coef: RED_ROWS doubles, hrows: the host's pinned slot or null */
+int dcgs_update(iemic_ctx* c, bool fused, const double* Q, int64_t ldq, int nv, double* hb, double* coef,
+                double* hrows, double* u, double* w, int64_t N, const int* act, int64_t own0, int64_t ps,
+                double* rrP)
+{
+    const dim3 g((unsigned)std::max<int64_t>(1, std::min<int64_t>(4096, (N / 2 + 255) / 256)));
+    if (fused) {
+        hipLaunchKernelGGL(k_dcgs_update<true>, g, dim3(256), 0, c->stream, Q, ldq, nv, hb, hrows, u, w, N, act,
+                           own0, ps, rrP);
+    } else {
+        hipLaunchKernelGGL(k_dcgs_coef, dim3(1), dim3(256), 0, c->stream, hb, nv, coef, hrows);
+        hipLaunchKernelGGL(k_dcgs_update<false>, g, dim3(256), 0, c->stream, Q, ldq, nv, coef, (double*)nullptr, u,
+                           w, N, act, own0, ps, rrP);
+    }
+    HIP_OK(hipGetLastError());
+    return 0;
 }
 
 /* x += sum_i y_i Z_i */
@@ -689,7 +753,7 @@ int fgmres(iemic_ctx* c, const double* b, double* x, const iemic_krylov* opt, ie
              * normalisation is folded in.  One read pass (k_dcgs_dot) + one update pass
              * (k_dcgs_update) over the basis per iteration; the Hessenberg column j-1 is final
              * (and the residual known) at iteration j.
-             * Pipelined: the update coefficients come from the device (k_dcgs_coef), so the
+             * Pipelined: the update pass forms its coefficients on the device (dcgs_scal), so the
              * host enqueues iteration jj+1 (update, preconditioner, SpMV, dot pass) before it
              * waits for iteration jj's dot rows; the queue never drains on a host round trip.
              * The one speculative iteration past convergence only touches columns the
@@ -703,8 +767,8 @@ int fgmres(iemic_ctx* c, const double* b, double* x, const iemic_krylov* opt, ie
             /* z_jj = M u_jj with u_jj of norm bt_jj: the Hessenberg column of z_jj / bt_jj is
              * the one assembled below, so the solution update divides y_jj by bt_jj */
             std::fill(zs.begin(), zs.end(), 1.0);
-            /* iteration jj: [update of jj-1 enqueued before] prec, SpMV, dot pass, coefficients,
-             * rows -> pinned slot jj % 2, update */
+            /* iteration jj: prec, SpMV, dot pass, update (coefficients in its prologue, rows ->
+             * pinned slot jj % 2) */
             auto enqueue = [&](int jj) -> int {
                 double* u = Q + (int64_t)jj * LQ;
                 double* wv = jj < m ? Q + (int64_t)(jj + 1) * LQ : nullptr;
@@ -742,13 +806,20 @@ int fgmres(iemic_ctx* c, const double* b, double* x, const iemic_krylov* opt, ie
                 hipLaunchKernelGGL(k_mdot_final, dim3(2 * nv + 3), dim3(256), 0, c->stream, c->d_part.p,
                                    nbx1, 2 * nv + 3, c->d_hbuf.p);
                 if ((rc2 = allreduce_sum(c, c->d_hbuf.p, 2 * nv + 3))) return rc2;
-                hipLaunchKernelGGL(k_dcgs_coef, dim3(1), dim3(256), 0, c->stream, c->d_hbuf.p, nv,
-                                   c->d_hbuf.p + RED_ROWS, c->h_red + (size_t)RED_ROWS * (jj & 1));
+                /* the update forms its coefficients itself and its first workgroup writes the
+                 * host's rows, so the rows' event follows it; the step after a full cycle's
+                 * last column has no update and gets the rows from k_dcgs_coef */
+                double* hrows = c->h_red + (size_t)RED_ROWS * (jj & 1);
+                if (jj < m) {
+                    if ((rc2 = dcgs_update(c, true, Q, LQ, nv, c->d_hbuf.p, nullptr, hrows, u, wv, NQ,
+                                           cmp ? (const int*)gs.act.act.p : nullptr, c->sub.own0,
+                                           (int64_t)c->sub.next, cmp ? gs.rrP.p : nullptr)))
+                        return rc2;
+                } else {
+                    hipLaunchKernelGGL(k_dcgs_coef, dim3(1), dim3(256), 0, c->stream, c->d_hbuf.p, nv,
+                                       c->d_hbuf.p + RED_ROWS, hrows);
+                }
                 HIP_OK(hipEventRecord(evr[jj & 1], c->stream));
-                if (jj < m)
-                    hipLaunchKernelGGL(k_dcgs_update, dim3((unsigned)std::min<int64_t>(4096, (NQ / 2 + 255) / 256)), dim3(256), 0, c->stream, Q, LQ, nv,
-                                       c->d_hbuf.p + RED_ROWS, u, wv, NQ, cmp ? (const int*)gs.act.act.p : nullptr,
-                                       c->sub.own0, (int64_t)c->sub.next, cmp ? gs.rrP.p : nullptr);
                 return 0;
             };
             if ((rc = enqueue(0))) return rc;

@@ -38,6 +38,13 @@ int ensure_krylov(iemic_ctx* c, int m, int64_t nc = 0);
 /* coefficients -> device through the pinned staging area (the previous use of the area
  * has completed: every caller synchronised the stream since) */
 int upload_coeffs(iemic_ctx* c, const double* h, int n);
+/* the DCGS2 update pass of one Arnoldi step on the context's stream, from the summed dot
+ * rows hb (2 nv + 5 doubles): fused (coefficients formed in the update's prologue, as the
+ * solve runs it) or as k_dcgs_coef + the update from its coefficient array coef (RED_ROWS
+ * doubles; the reference of test_hooks.hip).  hrows: the host's pinned slot, or null */
+int dcgs_update(iemic_ctx* c, bool fused, const double* Q, int64_t ldq, int nv, double* hb, double* coef,
+                double* hrows, double* u, double* w, int64_t N, const int* act, int64_t own0, int64_t ps,
+                double* rrP);
 
 }  // namespace iemic
 

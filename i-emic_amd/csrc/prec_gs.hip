@@ -1328,7 +1328,8 @@ static int gs_apply_tables(iemic_ctx* c)
 }
 
 /* the Schur matrix: every band builds the rows of its own columns, the sum over the ranks
- * is the whole matrix, factorised by cyclic reduction on every rank */
+ * is the whole matrix, factorised by cyclic reduction on every rank.  Stream-ordered on one
+ * rank (no host synchronisation); cr_check(gs.cr) follows */
 static int gs_schur_factor(iemic_ctx* c)
 {
     BlockGS& gs = c->gs;
@@ -1340,7 +1341,49 @@ static int gs_schur_factor(iemic_ctx* c)
                        c->d_val.p, gs.known.p, gs.uvinv.p, gs.gslot.p, gs.pw.p, gs.col_of_ij.p,
                        gs.pinned.p, lay_of(c->sub), c->sub.jb1, gs.S9.p);
     if ((rc = allreduce_sum(c, gs.S9.p, 9 * NC))) return rc;
-    if ((rc = cr_factor(c, gs.cr, gs.S9.p, gs.col_of_ij.p))) return rc;
+    return cr_factor(c, gs.cr, gs.S9.p, gs.col_of_ij.p);
+}
+
+/* The two factorisations of the set-up.  Both are dependent chains of small launches (the
+ * register Gauss-Jordan levels fill at most 96 of 256 CUs) that read only the Jacobian, the
+ * identity flags, the cell factors and the compact T/S couplings, and write only their own
+ * arrays: the Schur chain S9 and gs.cr, the T/S chain gs.mg (its levels' arrays and its own
+ * SchurCR gs.mg.cr); neither touches the context's reduction buffers.  One rank: the Schur
+ * chain is enqueued on the stream, then the T/S set-up runs with c->stream naming the side
+ * stream (forked after the apply tables; its host waits -- the coarsest level's pivot flag
+ * -- wait for the side stream alone, with the Schur chain already in the queue), the stream
+ * joins, and the Schur pivot flag is read after both.  Subdomains: both chains communicate
+ * (the all-reduce of S9, the T/S halo rows and the global coarsest problem), and the host
+ * and in-process transports synchronise the stream c->stream names, so the order stays
+ * serial there, the same on every rank.  IEMIC_SERIAL_SETUP=1 keeps it serial on one rank
+ * too (the same launches in the same per-chain order: the factors are bitwise the same). */
+static int gs_factor(iemic_ctx* c, int sweeps)
+{
+    BlockGS& gs = c->gs;
+    int rc;
+    if (c->serial_setup || c->sub.nranks > 1) {
+        if ((rc = gs_schur_factor(c))) return rc;
+        if ((rc = cr_check(c, gs.cr))) return rc;
+        return ts_mg_setup(c, sweeps);
+    }
+    hipStream_t s = c->stream;
+    HIP_OK(hipEventRecord(c->ev_fork, s));
+    HIP_OK(hipStreamWaitEvent(c->side, c->ev_fork, 0));
+    if ((rc = gs_schur_factor(c))) return rc;     /* nothing on the side stream yet */
+    c->stream = c->side;
+    rc = ts_mg_setup(c, sweeps);
+    c->stream = s;
+    /* join, also on the error path: no work of this set-up stays on the side stream */
+    hipError_t e = hipEventRecord(c->ev_join, c->side);
+    if (e == hipSuccess) e = hipStreamWaitEvent(s, c->ev_join, 0);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(c->side);
+        if (!rc) {
+            set_error(std::string("block GS set-up join: ") + hipGetErrorString(e));
+            rc = IEMIC_EDEVICE;
+        }
+    }
+    if (rc) return rc;
     return cr_check(c, gs.cr);
 }
 
@@ -1370,9 +1413,8 @@ int gs_compute(iemic_ctx* c, const iemic_krylov* opt)
     HIP_OK(hipMemsetAsync(gs.rrP.p, 0, sizeof(double) * gs.rrP.n, c->stream));
     c->kr.zclean = 0;
     if ((rc = gs_apply_tables(c))) return rc;
-    if ((rc = gs_schur_factor(c))) return rc;
     gs.ts_mg = opt ? std::max(0, opt->ts_mg) : 0;
-    if ((rc = ts_mg_setup(c, opt ? std::max(1, opt->mg_sweeps) : 1))) return rc;
+    if ((rc = gs_factor(c, opt ? std::max(1, opt->mg_sweeps) : 1))) return rc;
     gs.dyn_iters = opt ? std::max(1, opt->dyn_iters) : 1;
     gs.dyn_mr = opt ? (opt->dyn_mr != 0) : 0;
     gs.dyn_omega = opt && opt->dyn_omega > 0.0 ? opt->dyn_omega : 1.0;

@@ -1,7 +1,8 @@
 /*
  * test_hooks.h -- entry points that drive the dense solvers of the preconditioner on their
  * own (schur_cr.hip, band_lu.hip) for tests/test_gpu_dense.py, and the coupled model's
- * preconditioner (coupled.hip) for tests/test_gpu_coupled_krylov.py.  They are exported from the
+ * preconditioner (coupled.hip) for tests/test_gpu_coupled_krylov.py, and the DCGS2 update pass
+ * (krylov.hip) for tests/test_dcgs_fused_coef.py.  They are exported from the
  * device library but are NOT part of its public ABI (include/iemic.h, IEMIC_ABI_VERSION):
  * tests/dense_hooks.py binds them.  All pointers are host pointers; every hook runs on the
  * context's stream, owns its device buffers and returns the usual IEMIC_* codes.
@@ -56,6 +57,17 @@ int iemic_test_band_inverse(iemic_ctx* ctx, int N, int bl, int bu, double* ab, i
  * before every solve.  The device copy of z starts as NaN bit patterns, so an entry that
  * cpl_prec does not write comes back as NaN. */
 int iemic_test_coupled_prec(iemic_coupled* cm, const double* r_host, double* z_host, int use_prec);
+
+/* The DCGS2 update pass of one Arnoldi step (dcgs_update, krylov.hip) on host data: nv basis
+ * vectors Q (nv x ldq, ldq >= N even), the summed dot rows hb (2 nv + 5; rows 2 nv + 3, 2 nv + 4
+ * come back as beta, h_jj), u and w (N even; both overwritten).  fused != 0: the solve's
+ * launch, coefficients formed in the update's prologue; fused == 0: k_dcgs_coef and the
+ * update from its coefficient array.  hrows (2 nv + 5): what the kernels stored into the
+ * solve's pinned slot (NaN bit patterns where they stored nothing).  act != NULL (N a
+ * multiple of 6): the new w also goes into the planar rrP (6 planes of ps cells, cell act[a]
+ * < ps of compressed cell a; NaN bit patterns elsewhere). */
+int iemic_test_dcgs_update(iemic_ctx* ctx, int fused, int nv, int64_t N, int64_t ldq, const double* Q, double* hb,
+                           double* u, double* w, double* hrows, const int* act, int64_t ps, double* rrP);
 
 #ifdef __cplusplus
 }

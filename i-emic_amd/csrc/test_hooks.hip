@@ -1,8 +1,9 @@
 /*
- * test_hooks.hip -- the dense solvers of the preconditioner and the coupled model's block
- * Gauss-Seidel preconditioner driven on their own (test_hooks.h).  No kernels here: every
- * hook stages host data, calls the production entry points of schur_cr.hip / band_lu.hip /
- * coupled.hip on the context's stream and copies back.
+ * test_hooks.hip -- the dense solvers of the preconditioner, the coupled model's block
+ * Gauss-Seidel preconditioner and the DCGS2 update pass driven on their own (test_hooks.h).
+ * No kernels here: every hook stages host data, calls the production entry points of
+ * schur_cr.hip / band_lu.hip / coupled.hip / krylov.hip on the context's stream and copies
+ * back.
  */
 #include <algorithm>
 #include <cstring>
@@ -10,6 +11,7 @@
 
 #include "common.h"
 #include "coupled_internal.h"
+#include "krylov_internal.h"
 #include "test_hooks.h"
 
 using namespace iemic;
@@ -184,6 +186,46 @@ extern "C" int iemic_test_band_inverse(iemic_ctx* c, int N, int bl, int bu, doub
     if ((rc = d2h(c, ab, abd.p, sizeof(double) * N * W))) return rc;
     if ((rc = d2h(c, piv, pd.p, sizeof(int) * N))) return rc;
     return d2h(c, X, xd.p, sizeof(double) * N * N);
+}
+
+extern "C" int iemic_test_dcgs_update(iemic_ctx* c, int fused, int nv, int64_t N, int64_t ldq, const double* Q,
+                                      double* hb, double* u, double* w, double* hrows, const int* act, int64_t ps,
+                                      double* rrP)
+{
+    if (!c || !hb || !u || !w || !hrows || (nv > 0 && !Q)) return bad("null argument");
+    if (nv < 0 || nv > MAX_KRYLOV || N < 2 || (N & 1) || N > (1 << 24) || ldq < N || (ldq & 1)) return bad("DCGS2 shape out of range");
+    if (act && (!rrP || N % NUN || ps < N / NUN || ps > (1 << 24))) return bad("planar right-hand side out of range");
+    const int nr = 2 * nv + 5;
+    const int64_t ncell = N / NUN;
+    if (act)
+        for (int64_t a = 0; a < ncell; a++)
+            if (act[a] < 0 || act[a] >= ps) return bad("active cell outside the planes");
+    DevBuf<double> qd, hd, cd, ud, wd, rd;
+    DevBuf<int> ad;
+    if ((nv && qd.alloc((size_t)nv * ldq)) || hd.alloc(nr) || cd.alloc(RED_ROWS) || ud.alloc(N) || wd.alloc(N) ||
+        (act && (ad.alloc(ncell) || rd.alloc((size_t)NUN * ps))))
+        return IEMIC_ENOMEM;
+    int rc;
+    if (nv && (rc = h2d(c, qd.p, Q, sizeof(double) * nv * ldq))) return rc;
+    if ((rc = h2d(c, hd.p, hb, sizeof(double) * nr))) return rc;
+    if ((rc = h2d(c, ud.p, u, sizeof(double) * N))) return rc;
+    if ((rc = h2d(c, wd.p, w, sizeof(double) * N))) return rc;
+    HIP_OK(hipMemsetAsync(cd.p, 0xff, sizeof(double) * RED_ROWS, c->stream));
+    if (act) {
+        if ((rc = h2d(c, ad.p, act, sizeof(int) * ncell))) return rc;
+        HIP_OK(hipMemsetAsync(rd.p, 0xff, sizeof(double) * NUN * ps, c->stream));
+    }
+    /* the solve's pinned slot 0: the rows arrive there by the kernels' own stores */
+    std::memset(c->h_red, 0xff, sizeof(double) * nr);
+    if ((rc = dcgs_update(c, fused != 0, qd.p, ldq, nv, hd.p, cd.p, c->h_red, ud.p, wd.p, N, act ? ad.p : nullptr, 0,
+                          ps, act ? rd.p : nullptr)))
+        return rc;
+    if ((rc = d2h(c, hb, hd.p, sizeof(double) * nr))) return rc;
+    if ((rc = d2h(c, u, ud.p, sizeof(double) * N))) return rc;
+    if ((rc = d2h(c, w, wd.p, sizeof(double) * N))) return rc;
+    if (act && (rc = d2h(c, rrP, rd.p, sizeof(double) * NUN * ps))) return rc;
+    std::memcpy(hrows, c->h_red, sizeof(double) * nr);
+    return 0;
 }
 
 extern "C" int iemic_test_coupled_prec(iemic_coupled* cm, const double* r_host, double* z_host, int use_prec)
