@@ -151,10 +151,8 @@ static int dyn_halo_coefs(iemic_ctx* c)
     double* v = c->d_val.p;
     const int so = c->sub.nb[2], no = c->sub.nb[3];
     std::vector<Msg> y;
-    if (so >= 0) y.push_back({true, so, Seg{v, 0, NDS, row, nloc}});
-    if (no >= 0) y.push_back({false, no, Seg{as.dvh.p, row, NDS, row, 2 * row}});
-    if (no >= 0) y.push_back({true, no, Seg{v, nloc - row, NDS, row, nloc}});
-    if (so >= 0) y.push_back({false, so, Seg{as.dvh.p, 0, NDS, row, 2 * row}});
+    push_pair(y, so, no, Seg{v, 0, NDS, row, nloc}, Seg{as.dvh.p, row, NDS, row, 2 * row},
+              Seg{v, nloc - row, NDS, row, nloc}, Seg{as.dvh.p, 0, NDS, row, 2 * row});
     return run_msgs(c, y);
 }
 

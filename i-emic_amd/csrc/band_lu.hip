@@ -1,6 +1,6 @@
 /*
  * band_lu.hip -- LU factorisation and explicit inverse of a band matrix on the device
- * (the global coarsest problem of the T/S multigrid, ts_mg.hip).
+ * (the global coarsest problem of the T/S multigrid, ts_mg_setup.hip).
  */
 #include <algorithm>
 

@@ -159,9 +159,9 @@ int cr_solve(iemic_ctx* c, const SchurCR& cr, const double* b, double* x, hipStr
 int cr_inverse_dev(hipStream_t s, int m, const double* src, double* dst, int* info);
 int cr_inverse(hipStream_t s, int m, int count, const double* src, int s0, int sstep, double* dst, int* info);
 
-/* T/S aggregation multigrid of the block GS (ts_mg.hip; BlockGS::mg, which no other unit
- * names): 2x2 horizontal aggregates, full depth, band-local; level q has n[q] x m[q] x l cells
- * in the k-contiguous level layout (ts_mg.hip TsLev; level 0 packed from tsoff/tsdiag) with
+/* T/S aggregation multigrid of the block GS (ts_mg.hip, ts_mg_setup.hip; BlockGS::mg, which no
+ * other unit names): 2x2 horizontal aggregates, full depth, band-local; level q has n[q] x m[q] x l
+ * cells in the k-contiguous level layout (ts_mg_internal.h TsLev; level 0 packed from tsoff/tsdiag) with
  * 16 couplings, the 2x2 block, the z-line factors (12), rhs and iterate */
 struct TsMg {
     static constexpr int MAX = 12;
@@ -451,6 +451,49 @@ struct StreamGuard {
     iemic_ctx* c;
     ~StreamGuard() { if (c && c->stream) (void)dev_wait(c, nullptr, "return"); }
 };
+/* A scope whose work goes to the side stream.  The constructor forks (ev_fork on the stream,
+ * the side stream waits for it; err) and makes c->stream name the side stream, which all that
+ * reads c->stream follows (h2d, d2h, dev_zero, dev_wait, run_msgs, allreduce_sum,
+ * StreamGuard); the destructor puts the stream back on every return path.  fork_now = false:
+ * the caller forked earlier (OnSide::fork) and has put work on the stream since, which the
+ * side stream is not to wait for.  join: the stream is put back, ev_join follows the side
+ * stream's work and, when wait_now, the stream waits for it (else a later OnSide::wait).  A
+ * record or wait that fails is returned after the host has waited for the side stream
+ * instead, so none of the scope's work is left running unordered. */
+struct OnSide {
+    iemic_ctx* c;
+    hipStream_t main;
+    hipError_t err;
+    static hipError_t fork(iemic_ctx* c)
+    {
+        const hipError_t e = hipEventRecord(c->ev_fork, c->stream);
+        return e != hipSuccess ? e : hipStreamWaitEvent(c->side, c->ev_fork, 0);
+    }
+    static hipError_t wait(iemic_ctx* c)
+    {
+        const hipError_t e = hipStreamWaitEvent(c->stream, c->ev_join, 0);
+        if (e != hipSuccess) (void)hipStreamSynchronize(c->side);
+        return e;
+    }
+    explicit OnSide(iemic_ctx* c_, bool fork_now = true)
+        : c(c_), main(c_->stream), err(fork_now ? fork(c_) : hipSuccess)
+    {
+        c->stream = c->side;
+    }
+    OnSide(const OnSide&) = delete;
+    OnSide& operator=(const OnSide&) = delete;
+    ~OnSide() { c->stream = main; }
+    hipError_t join(bool wait_now)
+    {
+        c->stream = main;
+        const hipError_t e = hipEventRecord(c->ev_join, c->side);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(c->side);
+            return e;
+        }
+        return wait_now ? wait(c) : hipSuccess;
+    }
+};
 
 /* comm.hip: sums over the ranks (no-op for one rank) and halo exchanges.  A message is
  * nblk blocks of len doubles, stride doubles apart, from base + off; one exchange is a
@@ -465,6 +508,17 @@ struct Msg {
     int peer;
     Seg s;
 };
+/* the exchange with a pair of opposite neighbours (lo: west / south, hi: east / north; < 0:
+ * none) in the order by which the ranks' batches pair up: send lo, receive hi, send hi,
+ * receive lo */
+inline void push_pair(std::vector<Msg>& ops, int lo, int hi, const Seg& lo_send, const Seg& hi_recv,
+                      const Seg& hi_send, const Seg& lo_recv)
+{
+    if (lo >= 0) ops.push_back({true, lo, lo_send});
+    if (hi >= 0) ops.push_back({false, hi, hi_recv});
+    if (hi >= 0) ops.push_back({true, hi, hi_send});
+    if (lo >= 0) ops.push_back({false, lo, lo_recv});
+}
 int allreduce_sum(iemic_ctx* c, double* dev, int count);
 int comm_size(const iemic_ctx* c, int* size, int* kind);
 /* depth latitude rows and x columns of the ext layout (width doubles per cell) */

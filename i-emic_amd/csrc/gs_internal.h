@@ -1,6 +1,6 @@
 /*
  * gs_internal.h -- what the units of the block Gauss-Seidel preconditioner share
- * (prec_gs.hip, ts_mg.hip, active_set.hip): the Jacobian's slot indices, the subdomain
+ * (prec_gs.hip, ts_mg.hip, ts_mg_setup.hip, active_set.hip): the Jacobian's slot indices, the subdomain
  * layout seen by their kernels, and the launch helpers.  Included by nothing else.
  */
 #ifndef IEMIC_GS_INTERNAL_H

@@ -1366,22 +1366,15 @@ static int gs_factor(iemic_ctx* c, int sweeps)
         if ((rc = cr_check(c, gs.cr))) return rc;
         return ts_mg_setup(c, sweeps);
     }
-    hipStream_t s = c->stream;
-    HIP_OK(hipEventRecord(c->ev_fork, s));
-    HIP_OK(hipStreamWaitEvent(c->side, c->ev_fork, 0));
+    HIP_OK(OnSide::fork(c));
     if ((rc = gs_schur_factor(c))) return rc;     /* nothing on the side stream yet */
-    c->stream = c->side;
+    OnSide on(c, false);
     rc = ts_mg_setup(c, sweeps);
-    c->stream = s;
     /* join, also on the error path: no work of this set-up stays on the side stream */
-    hipError_t e = hipEventRecord(c->ev_join, c->side);
-    if (e == hipSuccess) e = hipStreamWaitEvent(s, c->ev_join, 0);
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(c->side);
-        if (!rc) {
-            set_error(std::string("block GS set-up join: ") + hipGetErrorString(e));
-            rc = IEMIC_EDEVICE;
-        }
+    const hipError_t e = on.join(true);
+    if (e != hipSuccess && !rc) {
+        set_error(std::string("block GS set-up join: ") + hipGetErrorString(e));
+        rc = IEMIC_EDEVICE;
     }
     if (rc) return rc;
     return cr_check(c, gs.cr);
@@ -1639,7 +1632,7 @@ static int gs_apply_impl(iemic_ctx* c, const double* r, double* z, bool cmp, boo
     }
     if (ts_at == gs.dyn_iters && (rc = ts())) return rc;
     if (ts_at < gs.dyn_iters && gs.ts_mg > 0) {
-        if (par) HIP_OK(hipStreamWaitEvent(s, c->ev_join, 0));   /* join */
+        if (par) HIP_OK(OnSide::wait(c));                        /* join */
         if ((rc = ts_mg_out(c, z))) return rc;
     }
     HIP_OK(hipGetLastError());

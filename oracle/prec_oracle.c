@@ -472,7 +472,7 @@ static void dyn_defect(gs_t* g, const double* z, double* d)
 
 
 
-/* ---- T/S aggregation multigrid (ts_mg.hip's ts_mg_setup / mg_vcycle restated on the
+/* ---- T/S aggregation multigrid (ts_mg_setup.hip's ts_mg_setup, ts_mg.hip's mg_vcycle on the
  * CPU, one band): levels of n x m x l cells merging 2x2 horizontal neighbours over the
  * full depth, Galerkin coarse operators with piecewise-constant transfers, z-line
  * (block-tridiagonal along k) relaxation by horizontal colour, forward before and
@@ -561,7 +561,7 @@ static void* mg_build(gs_t* g)
     M->periodic = g->periodic;
     int nn = n, mm = m, q = 0;
     M->n[0] = n; M->m[0] = m;
-    /* the GPU's one-rank rule (ts_mg.hip mg_levels): stop at the first level of <= 1024
+    /* the GPU's one-rank rule (ts_mg_setup.hip mg_levels): stop at the first level of <= 1024
      * cells whose longitudes fit a cyclic-reduction block (2 mm l <= 192, >= 2 longitudes),
      * solved exactly (the GPU by whole-problem cyclic reduction, here Gauss-Jordan) */
 #define MG_CR_OK(a, b) ((int64_t)(a) * (b) * l <= 1024 && 2 * (b) * l <= 192 && (a) >= 2)

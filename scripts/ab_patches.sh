@@ -757,12 +757,12 @@ PY
 
 ab_xh1() {
 # x halos on the first 1 intermediate T/S levels only
-sed -i "s/^constexpr int MG_XHALO_LEVELS = 99;/constexpr int MG_XHALO_LEVELS = 1;/" csrc/ts_mg.hip
+sed -i "s/^constexpr int MG_XHALO_LEVELS = 99;/constexpr int MG_XHALO_LEVELS = 1;/" csrc/ts_mg_internal.h
 }
 
 ab_xh2() {
 # x halos on the first 2 intermediate T/S levels only
-sed -i "s/^constexpr int MG_XHALO_LEVELS = 99;/constexpr int MG_XHALO_LEVELS = 2;/" csrc/ts_mg.hip
+sed -i "s/^constexpr int MG_XHALO_LEVELS = 99;/constexpr int MG_XHALO_LEVELS = 2;/" csrc/ts_mg_internal.h
 }
 
 v=${1:?variant}

@@ -5,8 +5,8 @@ against the same set-up in serial order (a context created under IEMIC_SERIAL_SE
 Both orders issue the same launches on the same data in the same per-chain order, so the
 factors -- and every apply and solve that uses them -- must be bitwise equal: no tolerance.
 
-Coarsest T/S level of each fixture (ts_mg.hip mg_levels: 2x2 coarsening until the level has at
-most 128 cells, stopping early at the first level of at most 1024 cells whose longitude blocks
+Coarsest T/S level of each fixture (ts_mg_setup.hip mg_levels: 2x2 coarsening until the level has
+at most 128 cells, stopping early at the first level of at most 1024 cells whose longitude blocks
 2 m l fit 192 unknowns):
   natl8      8 x  8 x  4 -> 4 x 4 x 4  =  64 cells, 128 unknowns: the dense device inverse
                                          (mg_coarse_dev, one k_cr_inv workgroup)
