@@ -184,6 +184,8 @@ struct TsMg {
      * longitudes (schur_cr.hip, the explicit "tail" inverse) */
     static constexpr int CR_CELLS = 1024;
     int crd = 0;
+    int ckind = 0;                   /* how cinv was assembled: 0 device, 1 cyclic reduction, 2 host */
+    bool nofuse = false;             /* test hook only: no level takes the fused launches    */
     int hr = 0;                      /* bands: level 0 has 2 halo rows, and its colour-1   */
                                      /* lines on them are relaxed here too (mg_vcycle)      */
     SchurCR cr;
@@ -196,6 +198,15 @@ int ts_mg_setup(iemic_ctx* c, int sweeps);
  * ts_mg_out.  side: the V-cycles on iemic_ctx::side, ev_join recorded after them */
 int ts_mg_solve(iemic_ctx* c, const double* zd, double* z, bool out, bool side);
 int ts_mg_out(iemic_ctx* c, double* z);
+/* test_hooks.hip: the V-cycle's plan and level q as the apply leaves it (device pointers; z is
+ * the iterate the level hands upward, cinv only on the coarsest level; halo: the level's
+ * layout pads its rows or columns) */
+struct TsMgProbe {
+    int nlev, lanes, sweeps, hr, ckind;
+    int n, m, par, colours, fused, halo;
+    const double *off, *diag, *b, *z, *cinv;
+};
+int ts_mg_probe(iemic_ctx* c, int q, TsMgProbe* o);
 
 /* band_lu.hip: band LU with partial pivoting and the explicit inverse, panels of BAND_NBP
  * columns (lpan: ceil(N / BAND_NBP) x (BAND_NBP + bl) x BAND_NBP multipliers) */

@@ -2,7 +2,9 @@
  * test_hooks.h -- entry points that drive the dense solvers of the preconditioner on their
  * own (schur_cr.hip, band_lu.hip) for tests/test_gpu_dense.py, and the coupled model's
  * preconditioner (coupled.hip) for tests/test_gpu_coupled_krylov.py, and the DCGS2 update pass
- * (krylov.hip) for tests/test_dcgs_fused_coef.py.  They are exported from the
+ * (krylov.hip) for tests/test_dcgs_fused_coef.py, and the T/S multigrid's plan, levels and
+ * fusion switch (iemic_test_ts_mg_plan, iemic_test_ts_mg_level, iemic_test_ts_mg_nofuse;
+ * ts_mg.hip, ts_mg_setup.hip) for tests/test_gpu_ts_mg.py.  They are exported from the
  * device library but are NOT part of its public ABI (include/iemic.h, IEMIC_ABI_VERSION):
  * tests/dense_hooks.py binds them.  All pointers are host pointers; every hook runs on the
  * context's stream, owns its device buffers and returns the usual IEMIC_* codes.
@@ -68,6 +70,21 @@ int iemic_test_coupled_prec(iemic_coupled* cm, const double* r_host, double* z_h
  * < ps of compressed cell a; NaN bit patterns elsewhere). */
 int iemic_test_dcgs_update(iemic_ctx* ctx, int fused, int nv, int64_t N, int64_t ldq, const double* Q, double* hb,
                            double* u, double* w, double* hrows, const int* act, int64_t ps, double* rrP);
+
+/* The T/S multigrid of the block Gauss-Seidel preconditioner as it was last set up (one rank).
+ * plan (IEMIC_TEST_PLAN_LEN ints): nlev, the lane count P, sweeps, hr, the coarsest level's
+ * assembly (0 device inverse, 1 cyclic reduction, 2 host), then per level n, m, par, the
+ * colour count and 1 where mg_fused holds. */
+int iemic_test_ts_mg_plan(iemic_ctx* ctx, int* plan);
+
+/* Level q after the last apply, in the halo-free order (component, jl, i, k): off (16 x ncl), diag
+ * (4 x ncl), the right-hand side b and the iterate z (2 x ncl each; z is the one the level
+ * hands upward, zu on a fused level), ncl = n m l; cinv ((2 ncl)^2, row-major) when q is the
+ * coarsest level (else it may be NULL). */
+int iemic_test_ts_mg_level(iemic_ctx* ctx, int q, double* off, double* diag, double* b, double* z, double* cinv);
+
+/* on != 0: no level is visited by the fused launches (k_mg_dn / k_mg_up) until it is cleared */
+int iemic_test_ts_mg_nofuse(iemic_ctx* ctx, int on);
 
 #ifdef __cplusplus
 }

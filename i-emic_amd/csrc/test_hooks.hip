@@ -1,6 +1,7 @@
 /*
  * test_hooks.hip -- the dense solvers of the preconditioner, the coupled model's block
- * Gauss-Seidel preconditioner and the DCGS2 update pass driven on their own (test_hooks.h).
+ * Gauss-Seidel preconditioner and the DCGS2 update pass driven on their own, and the T/S
+ * multigrid's plan and levels read back (test_hooks.h).
  * No kernels here: every hook stages host data, calls the production entry points of
  * schur_cr.hip / band_lu.hip / coupled.hip / krylov.hip on the context's stream and copies
  * back.
@@ -254,5 +255,60 @@ extern "C" int iemic_test_coupled_prec(iemic_coupled* cm, const double* r_host, 
     if ((rc = cpl_prec(cm, dr.p, dz.p, use_prec))) return rc;
     if ((rc = d2h(oc, packed.data(), dz.p, sizeof(double) * NC))) return rc;
     unpack_host(cm, packed, z_host);
+    return 0;
+}
+
+extern "C" int iemic_test_ts_mg_plan(iemic_ctx* c, int* plan)
+{
+    if (!c || !plan) return bad("null argument");
+    if (c->sub.nranks != 1) return bad("a single-rank context is needed");
+    if (!c->gs.ready || c->gs.ts_mg <= 0) return bad("no T/S multigrid set up");
+    std::fill(plan, plan + IEMIC_TEST_PLAN_LEN, 0);
+    TsMgProbe p;
+    int rc;
+    if ((rc = ts_mg_probe(c, 0, &p))) return bad("no T/S multigrid levels");
+    plan[0] = p.nlev;
+    plan[1] = p.lanes;
+    plan[2] = p.sweeps;
+    plan[3] = p.hr;
+    plan[4] = p.ckind;
+    for (int q = 0; q < p.nlev && 10 + 5 * q <= IEMIC_TEST_PLAN_LEN; q++) {
+        TsMgProbe l;
+        if ((rc = ts_mg_probe(c, q, &l))) return rc;
+        int* e = plan + 5 + 5 * q;
+        e[0] = l.n;
+        e[1] = l.m;
+        e[2] = l.par;
+        e[3] = l.colours;
+        e[4] = l.fused;
+    }
+    return 0;
+}
+
+extern "C" int iemic_test_ts_mg_level(iemic_ctx* c, int q, double* off, double* diag, double* b, double* z,
+                                      double* cinv)
+{
+    if (!c || !off || !diag || !b || !z) return bad("null argument");
+    if (c->sub.nranks != 1) return bad("a single-rank context is needed");
+    if (!c->gs.ready || c->gs.ts_mg <= 0) return bad("no T/S multigrid set up");
+    if (hipSetDevice(c->device) != hipSuccess) return IEMIC_EDEVICE;
+    TsMgProbe p;
+    if (ts_mg_probe(c, q, &p)) return bad("no such T/S multigrid level");
+    if (p.halo) return bad("the level's layout has a halo");
+    if (p.cinv && !cinv) return bad("null argument");
+    const size_t ncl = (size_t)p.n * p.m * c->l;
+    int rc;
+    if ((rc = d2h(c, off, p.off, sizeof(double) * 16 * ncl))) return rc;
+    if ((rc = d2h(c, diag, p.diag, sizeof(double) * 4 * ncl))) return rc;
+    if ((rc = d2h(c, b, p.b, sizeof(double) * 2 * ncl))) return rc;
+    if ((rc = d2h(c, z, p.z, sizeof(double) * 2 * ncl))) return rc;
+    if (p.cinv && (rc = d2h(c, cinv, p.cinv, sizeof(double) * 4 * ncl * ncl))) return rc;
+    return 0;
+}
+
+extern "C" int iemic_test_ts_mg_nofuse(iemic_ctx* c, int on)
+{
+    if (!c) return bad("null argument");
+    c->gs.mg.nofuse = on != 0;
     return 0;
 }

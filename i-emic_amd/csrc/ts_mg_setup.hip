@@ -620,6 +620,10 @@ int ts_mg_setup(iemic_ctx* c, int sweeps)
         gs.ts_mg = 0;
         return 0;
     }
+    /* latitude bands: level 0's halo rows (hr, mg_levels) follow the sweep count, which a live
+     * context may change between set-ups; the levels are then laid out again.  One rank: hr
+     * is 0 whatever the sweeps, so nothing changes there */
+    if (gs.mg.nlev && gs.mg.hr != (c->sub.npy > 1 && c->sub.npx == 1 && std::max(1, sweeps) == 1)) gs.mg.nlev = 0;
     if (gs.mg.nlev == 0) {
         if ((rc = mg_levels(c))) return rc;
         if (gs.ts_mg == 0) return 0;
@@ -628,8 +632,9 @@ int ts_mg_setup(iemic_ctx* c, int sweeps)
     const int qc = gs.mg.nlev - 1;
     const int64_t ncl = (int64_t)gs.mg.n[qc] * gs.mg.m[qc] * c->l;
     const int N = (int)(2 * ncl);
-    if (gs.mg.crd) return mg_coarse_cr(c, qc, ncl, N);
-    if (N <= 192 && c->sub.nranks <= 1) return mg_coarse_dev(c, qc, ncl, N);
+    gs.mg.ckind = gs.mg.crd ? 1 : (N <= 192 && c->sub.nranks <= 1) ? 0 : 2;
+    if (gs.mg.ckind == 1) return mg_coarse_cr(c, qc, ncl, N);
+    if (gs.mg.ckind == 0) return mg_coarse_dev(c, qc, ncl, N);
     return mg_coarse_host(c, qc, ncl, N);
 }
 

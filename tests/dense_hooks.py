@@ -1,6 +1,7 @@
 """ctypes binding of the device library's test hooks (i-emic_amd/csrc/test_hooks.h): the
 block cyclic reduction, the batched Gauss-Jordan inverse and the band LU of the
-preconditioner, each driven on its own.  Not part of the public ABI (include/iemic.h)."""
+preconditioner, each driven on its own, and the T/S multigrid's plan, levels and fusion
+switch.  Not part of the public ABI (include/iemic.h)."""
 import ctypes as C
 
 import numpy as np
@@ -28,6 +29,12 @@ def hooks():
         L.iemic_test_band_inverse.argtypes = [vp, i, i, i, _PD, _PI, _PD, _PI, _PI]
         L.iemic_test_coupled_prec.restype = i
         L.iemic_test_coupled_prec.argtypes = [vp, _PD, _PD, i]
+        L.iemic_test_ts_mg_plan.restype = i
+        L.iemic_test_ts_mg_plan.argtypes = [vp, _PI]
+        L.iemic_test_ts_mg_level.restype = i
+        L.iemic_test_ts_mg_level.argtypes = [vp, i] + [_PD] * 5
+        L.iemic_test_ts_mg_nofuse.restype = i
+        L.iemic_test_ts_mg_nofuse.argtypes = [vp, i]
         _bound = L
     return _bound
 
@@ -118,3 +125,37 @@ def band_inverse(h, N, bl, bu, ab, prefill=np.nan):
     rc = hooks().iemic_test_band_inverse(h, N, bl, bu, _d(ab), piv.ctypes.data_as(_PI), _d(X), C.byref(info),
                                          C.byref(so))
     return rc, ab, piv, X, info.value, so.value
+
+
+def ts_mg_plan(h):
+    """the T/S multigrid of context h as it was last set up: dict(nlev, lanes, sweeps, hr, kind,
+    sizes [(n, m)], par, colours, fused), keys as ts_mg_ref.expected_plan"""
+    plan = np.zeros(PLAN_LEN, dtype=np.int32)
+    rc = hooks().iemic_test_ts_mg_plan(h, plan.ctypes.data_as(_PI))
+    if rc:
+        raise RuntimeError(f"iemic_test_ts_mg_plan: {rc} {last_error()}")
+    nlev = int(plan[0])
+    lv = [[int(v) for v in plan[5 + 5 * q: 10 + 5 * q]] for q in range(nlev)]
+    return dict(nlev=nlev, lanes=int(plan[1]), sweeps=int(plan[2]), hr=int(plan[3]), kind=int(plan[4]),
+                sizes=[(e[0], e[1]) for e in lv], par=[e[2] for e in lv], colours=[e[3] for e in lv],
+                fused=[e[4] for e in lv])
+
+
+def ts_mg_level(h, q, n, m, l, coarsest):
+    """level q (n x m x l cells) after the last apply -> off (16, ncl), diag (4, ncl), b (2 ncl),
+    z (2 ncl), cinv ((2 ncl, 2 ncl) or None); cell (j n + i) l + k.  NaN-filled first, so an
+    entry the hook does not write cannot pass for a value."""
+    ncl = n * m * l
+    off, diag = np.full(16 * ncl, np.nan), np.full(4 * ncl, np.nan)
+    b, z = np.full(2 * ncl, np.nan), np.full(2 * ncl, np.nan)
+    cinv = np.full(4 * ncl * ncl, np.nan) if coarsest else None
+    rc = hooks().iemic_test_ts_mg_level(h, q, _d(off), _d(diag), _d(b), _d(z), _d(cinv))
+    if rc:
+        raise RuntimeError(f"iemic_test_ts_mg_level: {rc} {last_error()}")
+    return off.reshape(16, ncl), diag.reshape(4, ncl), b, z, None if cinv is None else cinv.reshape(2 * ncl, 2 * ncl)
+
+
+def ts_mg_nofuse(h, on):
+    rc = hooks().iemic_test_ts_mg_nofuse(h, int(bool(on)))
+    if rc:
+        raise RuntimeError(f"iemic_test_ts_mg_nofuse: {rc} {last_error()}")
