@@ -261,10 +261,17 @@ int assemble_jacobian(iemic_ctx* c, const double* x_dev)
     dim3 blk(128), grd((unsigned)((c->sub.nloc + 127) / 128), NUN);
     hipLaunchKernelGGL(k_jacobian, grd, blk, 0, c->stream, g, x_dev, c->d_val.p, c->sub.nloc,
                        (int64_t)c->rowintcon);
-    hipLaunchKernelGGL(k_diagB, dim3((unsigned)((c->sub.nloc + 255) / 256)), dim3(256), 0, c->stream,
-                       g, c->d_B.p, c->sub.nloc, (int64_t)c->rowintcon);
     HIP_OK(hipGetLastError());
+    if ((rc = assemble_diagB(c))) return rc;
     c->jac_valid = 1;
+    return 0;
+}
+
+int assemble_diagB(iemic_ctx* c)
+{
+    hipLaunchKernelGGL(k_diagB, dim3((unsigned)((c->sub.nloc + 255) / 256)), dim3(256), 0, c->stream,
+                       c->geo(), c->d_B.p, c->sub.nloc, (int64_t)c->rowintcon);
+    HIP_OK(hipGetLastError());
     return 0;
 }
 

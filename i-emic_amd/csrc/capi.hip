@@ -620,6 +620,18 @@ int host_sum(iemic_ctx* c, std::vector<double>& v)
     if (!rc) rc = d2h(c, v.data(), d.p, sizeof(double) * v.size());
     return rc;
 }
+/* max over the ranks (NaN propagates): each rank's value in its own slot, summed */
+int host_max(iemic_ctx* c, double* mx)
+{
+    if (c->sub.nranks <= 1) return 0;
+    std::vector<double> all((size_t)c->sub.nranks, 0.0);
+    all[(size_t)c->sub.rank] = *mx;
+    int rc = host_sum(c, all);
+    if (rc) return rc;
+    *mx = 0.0;
+    for (double v : all) *mx = (v > *mx || v != v) ? v : *mx;
+    return 0;
+}
 }  // namespace
 
 /* Epetra_Comm::SumAll over the context's ranks (host buffer, in place) */
@@ -1003,6 +1015,87 @@ extern "C" int iemic_newton_step(iemic_ctx* c, const iemic_krylov* opt, iemic_ne
     return inf.solve.converged ? 0 : IEMIC_ENOCONV;
 }
 
+/* ---- the theta time stepper (theta.hip) ------------------------------------------------ */
+/* ThetaModel::initStep (ThetaModel.H:64-74) */
+extern "C" int iemic_theta_init_step(iemic_ctx* c, double dt, double theta)
+{
+    CTX_CHECK(c);
+    return theta_init_step(c, dt, theta);
+}
+
+/* ThetaModel::computeRHS (ThetaModel.H:87-113) */
+extern "C" int iemic_theta_rhs(iemic_ctx* c, double* F)
+{
+    CTX_CHECK(c);
+    int rc = theta_rhs(c);
+    if (rc) return rc;
+    if (F) return get_ref(c, c->th.Ft.p, F);
+    DEV_SYNC(c);
+    return 0;
+}
+
+/* ThetaModel::computeJacobian (ThetaModel.H:118-146) */
+extern "C" int iemic_theta_jacobian(iemic_ctx* c)
+{
+    CTX_CHECK(c);
+    int rc = theta_jacobian(c);
+    if (rc) return rc;
+    DEV_SYNC(c);
+    return 0;
+}
+
+/* AdaptiveTransient.H:107 after a failed Newton run: the model is set back to x_n */
+extern "C" int iemic_theta_restore(iemic_ctx* c)
+{
+    CTX_CHECK(c);
+    return theta_restore(c);
+}
+
+/* one iteration of Newton.H:92-99 on the theta model: F_theta, J2, solve J2 dx = F_theta / dt /
+ * theta (ThetaModel.H:150-164), x -= dx, F_theta */
+extern "C" int iemic_theta_newton_step(iemic_ctx* c, const iemic_krylov* opt, int refactor,
+                                       iemic_theta_info* info)
+{
+    CTX_CHECK(c);
+    if (!opt) return IEMIC_EINVAL;
+    iemic_theta_info inf{};
+    using clk = std::chrono::steady_clock;
+    auto ms = [](clk::time_point a) { return std::chrono::duration<double, std::milli>(clk::now() - a).count(); };
+    auto T0 = clk::now();
+    auto t = clk::now();
+    int rc = theta_rhs(c);
+    if (rc) return rc;
+    DEV_SYNC(c);
+    inf.t_rhs_ms += ms(t);
+    inf.norm_f0 = std::sqrt(dot(c, c->th.Ft.p, c->th.Ft.p, 0));   /* NaN stays NaN */
+    t = clk::now();
+    if ((rc = theta_jacobian(c))) return rc;
+    DEV_SYNC(c);
+    inf.t_jac_ms = ms(t);
+    t = clk::now();
+    if (opt->prec > 0 && (refactor || !c->gs.ready)) {
+        if ((rc = prec_compute(c, opt))) return rc;
+        DEV_SYNC(c);
+    }
+    inf.t_prec_ms = ms(t);
+    t = clk::now();
+    if ((rc = krylov_solve(c, c->th.b.p, c->d_tmp2.p, opt, &inf.solve))) return rc;
+    DEV_SYNC(c);
+    inf.t_solve_ms = ms(t);
+    if ((rc = theta_update(c, c->d_tmp2.p, &inf.norm_dx))) return rc;
+    if ((rc = host_max(c, &inf.norm_dx))) return rc;
+    t = clk::now();
+    if ((rc = theta_rhs(c))) return rc;
+    DEV_SYNC(c);
+    inf.t_rhs_ms += ms(t);
+    inf.norm_f1 = std::sqrt(dot(c, c->th.Ft.p, c->th.Ft.p, 0));
+    c->jac_valid = 1;
+    inf.t_total_ms = ms(T0);
+    if (info) *info = inf;
+    /* as iemic_newton_step: the update is applied whatever the solver reported */
+    return inf.solve.converged ? 0 : IEMIC_ENOCONV;
+}
+
 /* ---- device vectors: the Epetra_Vector algebra Continuation.H applies through Utils
  * (dot / norm / update over the solve map), on vectors in the ext layout; the owned rows
  * are one contiguous slab, reductions are summed over the ranks ------------------------ */
@@ -1096,14 +1189,7 @@ extern "C" int iemic_vec_norm_inf(iemic_ctx* c, const double* x, double* out)
     if (rc) return rc;
     double mx = 0.0;
     for (double v : part) mx = (v > mx || v != v) ? v : mx;
-    if (c->sub.nranks > 1) {
-        /* max over the ranks: each rank's value in its own slot, summed */
-        std::vector<double> all((size_t)c->sub.nranks, 0.0);
-        all[(size_t)c->sub.rank] = mx;
-        if ((rc = host_sum(c, all))) return rc;
-        mx = 0.0;
-        for (double v : all) mx = (v > mx || v != v) ? v : mx;
-    }
+    if ((rc = host_max(c, &mx))) return rc;
     *out = mx;
     return 0;
 }

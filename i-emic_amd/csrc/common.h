@@ -333,6 +333,15 @@ struct Krylov {
                                      /* rows of the current set-up                        */
 };
 
+/* The theta time stepper's state (theta.hip; ThetaModel.H's timestep_, theta_, oldState_,
+ * oldRhs_): vectors in the ext layout, allocated at the first iemic_theta_init_step */
+struct Theta {
+    double theta = 1.0, dt = 0.0;
+    int init = 0;                    /* a step is initialised (xold, Fold current)        */
+    DevBuf<double> xold, Fold;       /* x_n and F(x_n)                                    */
+    DevBuf<double> Ft, b;            /* F_theta(x) and F_theta / dt / theta (the solve's rhs) */
+};
+
 constexpr int RED_BLOCKS = 1024;     /* partial-sum blocks of the reductions            */
 constexpr int MAX_KRYLOV = 1000;     /* largest Krylov dimension                        */
 /* reduction rows (DCGS2: 2 per basis vector + 3 sums + beta, h_jj; the coefficient area
@@ -392,6 +401,7 @@ struct iemic_ctx {
     int refs = 1;                    /* the handle + dependents (atmosphere, coupled model) */
     iemic::BlockGS gs;
     iemic::Krylov kr;
+    iemic::Theta th;
     iemic::Geo geo() const;
     iemic_ctx() = default;
     iemic_ctx(const iemic_ctx&) = delete;
@@ -558,6 +568,8 @@ void comm_destroy(iemic_ctx* c);
 /* assembly.hip */
 int assemble_jacobian(iemic_ctx* c, const double* x_dev);
 int assemble_rhs(iemic_ctx* c, const double* x_dev, double* F_dev);
+/* d_B = the diagonal mass matrix of the owned cells (state independent) */
+int assemble_diagB(iemic_ctx* c);
 int compute_forcing(iemic_ctx* c);
 /* the nine surface flux fields of the state x_dev (planar, [9][n*m], whole on every rank)
  * and the salinity correction times gamma, on the host */
@@ -575,6 +587,15 @@ int krylov_solve(iemic_ctx* c, const double* b, double* x, const iemic_krylov* o
                  iemic_solve_info* info);
 int fgmres(iemic_ctx* c, const double* b, double* x, const iemic_krylov* opt,
            iemic_solve_info* info);
+/* theta.hip: the theta method on the resident state (ThetaModel.H:64-164) */
+int theta_init_step(iemic_ctx* c, double dt, double theta);
+/* F_theta(state) into Theta::Ft, scaled by 1 / dt / theta into Theta::b */
+int theta_rhs(iemic_ctx* c);
+/* J(state) with -B / dt / theta on the diagonal of the U, V, T and S rows */
+int theta_jacobian(iemic_ctx* c);
+/* state -= dx on the owned rows; *absmax: this rank's max |dx| (NaN propagates) */
+int theta_update(iemic_ctx* c, const double* dx, double* absmax);
+int theta_restore(iemic_ctx* c);
 /* prec.hip */
 int prec_compute(iemic_ctx* c, const iemic_krylov* opt);
 int prec_apply(iemic_ctx* c, const double* r, double* z);

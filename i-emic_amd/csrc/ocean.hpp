@@ -208,6 +208,32 @@ class Ocean {
         return info;
     }
 
+    /* ---- the theta time stepper: what ThetaModel<Ocean> lays over the model -------- */
+    /* ThetaModel::initStep (ThetaModel.H:64-74): x_n <- state, F_n <- F(x_n), and its
+     * preProcess: the preconditioner is refactored at the step's first solve */
+    void thetaInitStep(double dt, double theta)
+    {
+        check(iemic_theta_init_step(ctx_, dt, theta), "thetaInitStep");
+        preProcess();
+    }
+    /* ThetaModel::computeRHS (ThetaModel.H:87-113): F_theta in getRHS() */
+    void thetaRHS() { check(iemic_theta_rhs(ctx_, rhs_->data()), "thetaRHS"); }
+    /* ThetaModel::computeJacobian (ThetaModel.H:118-146): solve, applyMatrix and
+     * buildPreconditioner then act on J - B / dt / theta */
+    void thetaJacobian() { check(iemic_theta_jacobian(ctx_), "thetaJacobian"); }
+    void thetaRestore() { check(iemic_theta_restore(ctx_), "thetaRestore"); }
+    /* one iteration of Newton.H:92-99 on the theta model, on the device; the update is
+     * applied even when the linear solve missed its tolerance (info.solve.converged) */
+    iemic_theta_info thetaNewtonStep()
+    {
+        iemic_theta_info info{};
+        const int rc = iemic_theta_newton_step(ctx_, &krylov_, recompPrec_ ? 1 : 0, &info);
+        if (rc != IEMIC_ENOCONV) check(rc, "thetaNewtonStep");
+        recompPrec_ = false;
+        lastSolve_ = info.solve;
+        return info;
+    }
+
     size_t nrows() const { return N_; }
     iemic_ctx* handle() { return ctx_; }
 

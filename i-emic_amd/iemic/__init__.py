@@ -9,11 +9,14 @@ from .config import THCMConfig, landmask, preset, synthetic_state
 from ._lib import IemicError
 
 __all__ = ["config", "THCMConfig", "landmask", "preset", "synthetic_state", "IemicError",
-           "Ocean"]
+           "Ocean", "ThetaStepper"]
 
 
 def __getattr__(name):
     if name == "Ocean":
         from .ocean import Ocean
         return Ocean
+    if name == "ThetaStepper":
+        from .transient import ThetaStepper
+        return ThetaStepper
     raise AttributeError(name)

@@ -650,6 +650,47 @@ class Ocean:
         check(rc, "iemic_newton_step")
         return info
 
+    # ---- the theta time stepper (ThetaModel<Ocean>; driven by iemic.transient) ---------
+    def thetaInitStep(self, dt: float, theta: float) -> None:
+        """ThetaModel::initStep (ThetaModel.H:64-74): x_n <- state, F_n <- F(x_n).  theta
+        outside (0, 1] and dt <= 0 raise IemicError by name."""
+        check(lib().iemic_theta_init_step(self._h, float(dt), float(theta)), "iemic_theta_init_step")
+
+    def thetaRHS(self) -> np.ndarray:
+        """F_theta(state) = dt theta F + dt (1 - theta) F_n + B (x_n - x) (ThetaModel.H:87-113)."""
+        check(lib().iemic_theta_rhs(self._h, ptr(self._F)), "iemic_theta_rhs")
+        return self._F
+
+    def thetaJacobian(self) -> None:
+        """J2 = J - B / dt / theta (ThetaModel.H:118-146); exportCSR, applyMatrix,
+        buildPreconditioner and solve then act on J2, diagB still returns B."""
+        check(lib().iemic_theta_jacobian(self._h), "iemic_theta_jacobian")
+
+    def thetaRestore(self) -> None:
+        """state <- x_n (after a failed Newton run, AdaptiveTransient.H:107)."""
+        check(lib().iemic_theta_restore(self._h), "iemic_theta_restore")
+
+    def thetaNewtonStep(self, allow_unconverged: bool = True) -> _lib.ThetaInfo:
+        """One iteration of Newton.H:92-99 on the theta model, on the device: J2, the
+        preconditioner if preProcess flagged it (once per time step), J2 dx = F_theta / dt /
+        theta, x -= dx, F_theta.  The update is applied whatever the linear solver reported,
+        as Newton.H does; allow_unconverged=False raises when it missed its tolerance."""
+        k = self._krylov()
+        info = _lib.ThetaInfo()
+        rc = lib().iemic_theta_newton_step(self._h, C.byref(k), int(self._recomp_prec), C.byref(info))
+        if rc in (0, _lib.IEMIC_ENOCONV):
+            self._recomp_prec = False
+        if rc == _lib.IEMIC_ENOCONV and not allow_unconverged:
+            raise _lib.IemicError(
+                f"iemic_theta_newton_step: the linear solve did not converge ({info.solve.iters} steps, "
+                f"relative residual {info.solve.explicit_rel_res:.3e})")
+        if rc != _lib.IEMIC_ENOCONV:
+            check(rc, "iemic_theta_newton_step")
+        self.last_solve = info.solve
+        if self.solve_hook is not None:
+            self.solve_hook(info.solve)
+        return info
+
     # ---- inspection -----------------------------------------------------------------
     def exportCSR(self):
         nnz = lib().iemic_graph_nnz(self._h)

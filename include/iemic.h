@@ -45,9 +45,9 @@ extern "C" {
 
 /* Version of this header's structs and entry points.  Bumped whenever a struct changes
  * size or meaning (5: iemic_solve_info gained `safeguard` in round 4, the device vector
- * algebra of round 5; 7: surface fluxes and inserted forcing fields); a caller built against another header must refuse to run:
+ * algebra of round 5; 7: surface fluxes and inserted forcing fields; 8: the theta time stepper); a caller built against another header must refuse to run:
  *   if (iemic_abi_version() != IEMIC_ABI_VERSION) abort(); */
-#define IEMIC_ABI_VERSION 7
+#define IEMIC_ABI_VERSION 8
 int iemic_abi_version(void);
 
 typedef struct iemic_ctx iemic_ctx;
@@ -378,6 +378,37 @@ typedef struct {
     double t_jac_ms, t_rhs_ms, t_prec_ms, t_solve_ms, t_total_ms;
 } iemic_newton_info;
 int iemic_newton_step(iemic_ctx* ctx, const iemic_krylov* opt, iemic_newton_info* info);
+
+/* ---- the theta time stepper on the resident state (src/transient/ThetaModel.H under
+ * Newton.H and AdaptiveTransient.H; the stepping loop itself is the caller's, iemic/transient.py).
+ * With x_n the state at iemic_theta_init_step, F_n = F(x_n) and B the diagonal mass matrix:
+ *   F_theta(x) = dt theta F(x) + dt (1 - theta) F_n + B (x_n - x)   (summed in this order)
+ *   J2 = J + diag(-B / dt / theta)                                   (divisions in this order)
+ * Every call but iemic_theta_init_step returns IEMIC_ESTATE before the first init_step. */
+/* ThetaModel::initStep (ThetaModel.H:64-74): x_n <- state, F_n <- F(x_n).  theta outside
+ * (0, 1] and dt <= 0 are refused with IEMIC_EINVAL (theta = 0 would divide by B, which is zero
+ * on the W, P, land and integral-condition rows) */
+int iemic_theta_init_step(iemic_ctx* ctx, double dt, double theta);
+/* ThetaModel::computeRHS (ThetaModel.H:87-113): F_theta at the state, reference row order;
+ * F may be NULL */
+int iemic_theta_rhs(iemic_ctx* ctx, double* F);
+/* ThetaModel::computeJacobian (ThetaModel.H:118-146): J2 at the state.  iemic_export_csr,
+ * iemic_spmv, iemic_prec_compute and iemic_solve then act on J2; iemic_diag_b still returns B */
+int iemic_theta_jacobian(iemic_ctx* ctx);
+/* AdaptiveTransient.H:107 after a failed Newton run: state <- x_n */
+int iemic_theta_restore(iemic_ctx* ctx);
+/* One iteration of Newton.H:92-99 over the theta model, vectors resident in HBM: F_theta, J2,
+ * the preconditioner when `refactor` is set (ThetaModel::initStep's preProcess: once per time
+ * step) or none exists, J2 dx = F_theta / dt / theta (ThetaModel.H:150-164), x <- x - dx,
+ * F_theta.  Returns 0 or IEMIC_ENOCONV, the update applied either way. */
+typedef struct {
+    double norm_f0, norm_f1;     /* ||F_theta||_2 before / after the update          */
+    double norm_dx;              /* ||dx||_inf (over all ranks; NaN propagates)      */
+    iemic_solve_info solve;
+    double t_jac_ms, t_rhs_ms, t_prec_ms, t_solve_ms, t_total_ms;
+} iemic_theta_info;
+int iemic_theta_newton_step(iemic_ctx* ctx, const iemic_krylov* opt, int refactor,
+                            iemic_theta_info* info);
 
 /* ---- profiling helpers (bench): time n launches of the SpMV kernel with HIP events
  * on the stream it runs on; returns mean kernel milliseconds. */
