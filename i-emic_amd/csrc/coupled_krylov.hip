@@ -1,14 +1,15 @@
 /*
  * coupled_krylov.hip -- the Krylov solvers of the coupled model on packed vectors
- * [ocean owned rows | atmosphere]: iemic_coupled_solve with coupled_fgmres and coupled_idrs.
+ * [ocean owned rows | atmosphere]: iemic_coupled_solve with coupled_fgmres and IDR(s).
  *
- * They share the element-wise vector kernels (vec_kernels.h) and the Hessenberg code
- * (hessenberg.h) with the ocean's fgmres and idrs (krylov.hip, idrs.hip), but not their
- * reductions or schedules: the dots here reduce over KB = 512 blocks with an LDS tree,
- * coupled_idrs synchronises after every dot, and coupled_fgmres runs CGS2 with the
+ * IDR(s) is idrs_run (idrs_core.h), the loop the ocean's idrs runs (idrs.hip), over
+ * CoupledSpace below.  The solvers share the element-wise vector kernels (vec_kernels.h) and
+ * the Hessenberg code (hessenberg.h) with the ocean's, but not their reductions: the dots here
+ * reduce over KB = 512 blocks with an LDS tree, and coupled_fgmres runs CGS2 with the
  * coefficients left on the device.  Operator and preconditioner: coupled.hip.
  */
 #include <algorithm>
+#include <cassert>
 #include <chrono>
 #include <cmath>
 #include <vector>
@@ -16,6 +17,7 @@
 #include "common.h"
 #include "coupled_internal.h"
 #include "hessenberg.h"
+#include "idrs_core.h"
 #include "vec_kernels.h"
 
 using namespace iemic;
@@ -71,13 +73,7 @@ __global__ void k_cidr_random(double* __restrict__ P, int64_t ld, int s, int64_t
 {
     const int64_t q0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (q0 >= N) return;
-    for (int q = 0; q < s; q++) {
-        uint64_t z = 0x9E3779B97F4A7C15ull * ((uint64_t)q0 * 16 + (uint64_t)q + 1) + 20261017ull;
-        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-        z ^= z >> 31;
-        P[(int64_t)q * ld + q0] = 2.0 * ((double)(z >> 11) * (1.0 / 9007199254740992.0)) - 1.0;
-    }
+    for (int q = 0; q < s; q++) P[(int64_t)q * ld + q0] = idr_shadow_entry((uint64_t)q0, q, 20261017ull);
 }
 /* y -= sum_v c_v X_v with the coefficients in device memory (CGS2 pass without a host trip) */
 __global__ void k_cupdate_m(const double* __restrict__ X, int64_t ld, int nv, const double* __restrict__ c,
@@ -128,160 +124,72 @@ double cdot_host(iemic_coupled* cm, const double* V, int64_t ld, int nv, const d
     return out[nv];
 }
 
-void clin(iemic_coupled* cm, double a, double* y, const std::vector<double>& cs, const std::vector<const double*>& xs)
-{
-    hipLaunchKernelGGL(k_lincomb, dim3(blocks_for(cm->NC)), dim3(256), 0, cm->oc->stream, make_lc(a, cs, xs, 0), y,
-                       cm->NC);
-}
-void clin2(iemic_coupled* cm, double a1, double* y1, const std::vector<double>& c1, const std::vector<const double*>& x1,
-           double a2, double* y2, const std::vector<double>& c2, const std::vector<const double*>& x2)
-{
-    hipLaunchKernelGGL(k_lincomb2, dim3(blocks_for(cm->NC)), dim3(256), 0, cm->oc->stream, make_lc(a1, c1, x1, 0), y1,
-                       make_lc(a2, c2, x2, 0), y2, cm->NC);
-}
-
-/* IDR(s) on the packed coupled vector (IDRSolver.H:109-340: the same restatement as the
- * ocean's idrs (idrs.hip) -- bi-orthogonalisation against the shadow space P, omega with
- * the angle safeguard, optional residual replacement), right preconditioned by the block
- * Gauss-Seidel preconditioner.  b, x: device packed vectors; x starts at 0. */
-int coupled_idrs(iemic_coupled* cm, const double* b, double* x, const iemic_krylov* opt, double normb,
-                 iemic_solve_info& inf)
-{
-    hipStream_t st = cm->oc->stream;
-    const int s = std::max(1, std::min(opt->idr_s > 0 ? opt->idr_s : 4, 8));
-    const double angle = opt->idr_angle > 0.0 ? opt->idr_angle : 0.7;
-    const double mp = 1e-13;
-    const int maxit = std::max(1, opt->krylov_dim * (opt->max_restarts + 1));
-    const int64_t NC = cm->NC;
-    const int need = 3 * s + 3;
-    if (cm->mk < need) {
-        if (cm->V.alloc((size_t)(need + 1) * NC) || cm->Z.alloc((size_t)need * NC)) {
-            set_error("coupled IDR(s): out of device memory");
-            return IEMIC_ENOMEM;
+/* the packed vectors as idrs_run takes them (idrs_core.h), right preconditioned by the block
+ * Gauss-Seidel preconditioner; storage in cm->V (and cm->Z, which coupled_fgmres sizes with it) */
+struct CoupledSpace {
+    iemic_coupled* cm;
+    int prec_on;
+    int64_t ld;                                  /* NC */
+    hipStream_t stream;
+    unsigned GR;
+    int work(int nvec, double*& base)
+    {
+        if (cm->mk < nvec) {
+            if (cm->V.alloc((size_t)(nvec + 1) * ld) || cm->Z.alloc((size_t)nvec * ld)) {
+                set_error("coupled IDR(s): out of device memory");
+                return IEMIC_ENOMEM;
+            }
+            cm->mk = nvec;
         }
-        cm->mk = need;
+        base = cm->V.p;
+        return 0;
     }
-    double* P = cm->V.p;
-    double* U = P + (int64_t)s * NC;
-    double* G = U + (int64_t)s * NC;
-    double* t = G + (int64_t)s * NC;
-    double* r = t + NC;
-    double* v = r + NC;
-    auto Ui = [&](int i) { return U + (int64_t)i * NC; };
-    auto Gi = [&](int i) { return G + (int64_t)i * NC; };
-    auto Pi = [&](int i) { return P + (int64_t)i * NC; };
-    std::vector<double> tmp(s + 2);
-    int rc = 0;
-    hipLaunchKernelGGL(k_cidr_random, dim3((unsigned)((NC + 255) / 256)), dim3(256), 0, st, P, NC, s, NC);
-    for (int j = 0; j < s; j++) {
-        if (j > 0) {
-            cdot_host(cm, P, NC, j, Pi(j), tmp.data());
-            std::vector<double> cs;
-            std::vector<const double*> xs;
-            for (int k = 0; k < j; k++) { cs.push_back(-tmp[k]); xs.push_back(Pi(k)); }
-            clin(cm, 1.0, Pi(j), cs, xs);
-        }
-        const double nn = std::sqrt(std::max(0.0, cdot_host(cm, nullptr, 0, 0, Pi(j), tmp.data())));
-        hipLaunchKernelGGL(k_scale_copy, dim3(blocks_for(NC)), dim3(256), 0, st, (const double*)Pi(j), 1.0 / nn, Pi(j), NC);
+    void shadow(double* P, int s)
+    {
+        hipLaunchKernelGGL(k_cidr_random, dim3((unsigned)((ld + 255) / 256)), dim3(256), 0, stream, P, ld, s, ld);
     }
-    HIP_OK(hipMemcpyAsync(r, b, sizeof(double) * NC, hipMemcpyDeviceToDevice, st));
-    const double tolb = opt->tol * normb;
-    double normr = normb;
-    std::vector<double> f(s + 1, 0.0), gamma(s, 0.0), d(s + 2, 0.0);
-    std::vector<std::vector<double>> M(s, std::vector<double>(s, 0.0));
-    double om = 1.0;
-    int jj = 0, iter = 0;
-    bool trueres = false;
-    auto prec = [&](const double* in, double* out) { return cpl_prec(cm, in, out, opt->prec > 0); };
-    while (normr > tolb && iter < maxit) {
-        cdot_host(cm, P, NC, s, r, f.data());                         /* f = P' r */
-        for (int k = 0; k < s; k++) {
-            if (jj > 0) {
-                std::vector<double> cs{1.0};
-                std::vector<const double*> xs{r};
-                for (int i = k; i < s; i++) {
-                    double gi = f[i];
-                    for (int j = k; j < i; j++) gi -= M[i][j] * gamma[j];
-                    gamma[i] = gi / M[i][i];
-                    cs.push_back(-gamma[i]);
-                    xs.push_back(Gi(i));
-                }
-                clin(cm, 0.0, v, cs, xs);                                    /* v = r - G gamma */
-                if ((rc = prec(v, t))) return rc;
-                cs.assign(1, om);
-                xs.assign(1, t);
-                for (int i = k; i < s; i++) { cs.push_back(gamma[i]); xs.push_back(Ui(i)); }
-                clin(cm, 0.0, Ui(k), cs, xs);
-            } else {
-                if ((rc = prec(r, Ui(k)))) return rc;
-            }
-            if ((rc = cpl_apply(cm, Ui(k), Gi(k)))) return rc;
-            cdot_host(cm, P, NC, s, Gi(k), d.data());
-            std::vector<double> al(k, 0.0);
-            for (int i = 0; i < k; i++) {
-                double a = d[i];
-                for (int j = 0; j < i; j++) a -= al[j] * M[i][j];
-                al[i] = a / M[i][i];
-            }
-            for (int i = k; i < s; i++) {
-                double mik = d[i];
-                for (int j = 0; j < k; j++) mik -= al[j] * M[i][j];
-                M[i][k] = mik;
-            }
-            if (k > 0) {
-                std::vector<double> cs;
-                std::vector<const double*> xg, xu;
-                for (int i = 0; i < k; i++) { cs.push_back(-al[i]); xg.push_back(Gi(i)); xu.push_back(Ui(i)); }
-                clin2(cm, 1.0, Gi(k), cs, xg, 1.0, Ui(k), cs, xu);
-            }
-            if (!std::isfinite(M[k][k]) || M[k][k] == 0.0) {
-                set_error("coupled IDR(s): breakdown");
-                return IEMIC_ERANGE;
-            }
-            const double beta = f[k] / M[k][k];
-            clin2(cm, 1.0, r, {-beta}, {Gi(k)}, 1.0, x, {beta}, {Ui(k)});
-            normr = std::sqrt(std::max(0.0, cdot_host(cm, nullptr, 0, 0, r, tmp.data())));
-            if (!std::isfinite(normr)) {
-                set_error("coupled IDR(s): non-finite residual");
-                return IEMIC_ERANGE;
-            }
-            if (opt->idr_replace && normr > tolb / mp) trueres = true;
-            for (int i = k + 1; i < s; i++) f[i] -= beta * M[i][k];
-            iter++;
-            if (normr < tolb || iter >= maxit) break;
-        }
-        if (normr < tolb || iter >= maxit) break;
-        jj++;
-        if ((rc = prec(r, v))) return rc;
-        if ((rc = cpl_apply(cm, v, t))) return rc;
-        double tt_tr[2];
-        cdot_host(cm, r, NC, 1, t, tmp.data());                      /* r.t, t.t */
-        tt_tr[0] = tmp[1];
-        tt_tr[1] = tmp[0];
-        const double nt = std::sqrt(std::max(0.0, tt_tr[0])), ts = tt_tr[1];
-        if (!(nt > 0.0) || !std::isfinite(ts)) {
-            set_error("coupled IDR(s): breakdown in omega");
-            return IEMIC_ERANGE;
-        }
-        const double rho = std::fabs(ts / (nt * normr));
-        om = ts / (nt * nt);
-        if (rho < angle) om = om * angle / rho;
-        clin2(cm, 1.0, r, {-om}, {t}, 1.0, x, {om}, {v});
-        normr = std::sqrt(std::max(0.0, cdot_host(cm, nullptr, 0, 0, r, tmp.data())));
-        if (opt->idr_replace && normr > tolb / mp) trueres = true;
-        if (trueres && normr < normb) {
-            if ((rc = cpl_apply(cm, x, r))) return rc;
-            hipLaunchKernelGGL(k_axpby, dim3(blocks_for(NC)), dim3(256), 0, st, 1.0, b, -1.0, (const double*)r, r, NC);
-            normr = std::sqrt(std::max(0.0, cdot_host(cm, nullptr, 0, 0, r, tmp.data())));
-            trueres = false;
-            inf.reorth++;
-        }
-        iter++;
+    /* V_v . w from one cdot_dev (whose slot nv holds w . w), ea . ea from a second one into
+     * slot nv unless it is that w . w; one copy and one wait */
+    int mdot(const double* V, int nv, const double* w, double* out, const double* ea = nullptr,
+             const double* eb = nullptr)
+    {
+        assert(ea == eb);
+        int rc = 0;
+        if (nv > 0 && (rc = cdot_dev(cm, V, ld, nv, w, cm->hb.p))) return rc;
+        if (ea && (nv == 0 || ea != w) && (rc = cdot_dev(cm, nullptr, 0, 0, ea, cm->hb.p + nv))) return rc;
+        const int nout = nv + (ea ? 1 : 0);
+        HIP_OK(hipMemcpyAsync(cm->h_red, cm->hb.p, sizeof(double) * nout, hipMemcpyDeviceToHost, stream));
+        if ((rc = dev_wait(cm->oc, nullptr, "coupled dots"))) return rc;
+        std::copy(cm->h_red, cm->h_red + nout, out);
+        return 0;
     }
-    inf.iters = iter;
-    inf.implicit_rel_res = normr / normb;
-    return 0;
-}
+    int norm2(const double* a, double* out) { return mdot(nullptr, 0, nullptr, out, a, a); }
+    void lincomb(double a, double* y, const Coefs& cs, const Vecs& xs)
+    {
+        hipLaunchKernelGGL(k_lincomb, dim3(GR), dim3(256), 0, stream, make_lc(a, cs, xs, 0), y, ld);
+    }
+    void lincomb2(double a1, double* y1, const Coefs& c1, const Vecs& x1, double a2, double* y2, const Coefs& c2,
+                  const Vecs& x2)
+    {
+        hipLaunchKernelGGL(k_lincomb2, dim3(GR), dim3(256), 0, stream, make_lc(a1, c1, x1, 0), y1, make_lc(a2, c2, x2, 0),
+                           y2, ld);
+    }
+    void scale(double* y, double a)
+    {
+        hipLaunchKernelGGL(k_scale_copy, dim3(GR), dim3(256), 0, stream, (const double*)y, a, y, ld);
+    }
+    void axpby(double a, const double* x, double b, const double* y, double* out)
+    {
+        hipLaunchKernelGGL(k_axpby, dim3(GR), dim3(256), 0, stream, a, x, b, y, out, ld);
+    }
+    int copy(double* dst, const double* src)
+    {
+        HIP_OK(hipMemcpyAsync(dst, src, sizeof(double) * ld, hipMemcpyDeviceToDevice, stream));
+        return 0;
+    }
+    int prec(const double* in, double* out) { return cpl_prec(cm, in, out, prec_on); }
+    int apply(const double* in, double* out) { return cpl_apply(cm, in, out); }
+};
 
 /* r = b - A x on packed device vectors (w: scratch); returns ||r|| */
 double coupled_residual(iemic_coupled* cm, const double* b, const double* x, double* w, double* r, int* rc)
@@ -424,6 +332,7 @@ extern "C" int iemic_coupled_solve(iemic_coupled* cm, const double* b_host, doub
     iemic_solve_info inf{};
     std::vector<double> tmp(1);
     const double bnorm = std::sqrt(std::max(cdot_host(cm, nullptr, 0, 0, db.p, tmp.data()), 0.0));
+    if (!std::isfinite(bnorm)) return nonfinite();
     if (!(bnorm > 0)) {
         inf.converged = 1;
         if (info) *info = inf;
@@ -431,7 +340,8 @@ extern "C" int iemic_coupled_solve(iemic_coupled* cm, const double* b_host, doub
         return 0;
     }
     if (opt->method == 1) {
-        if ((rc = coupled_idrs(cm, db.p, dxv.p, opt, bnorm, inf))) return rc;
+        CoupledSpace sp{cm, opt->prec > 0, NC, oc->stream, blocks_for(NC)};
+        if ((rc = idrs_run(sp, db.p, dxv.p, opt, bnorm, inf))) return rc;
         inf.explicit_rel_res = coupled_residual(cm, db.p, dxv.p, cm->w.p, cm->r.p, &rc) / bnorm;
         if (rc) return rc;
     } else {

@@ -1,7 +1,8 @@
 /*
  * krylov_internal.h -- what the ocean's Krylov units share (krylov.hip, idrs.hip): the launch
  * grid of their element-wise kernels, the small numeric guards, and the helpers of krylov.hip
- * that IDR(s) calls.  Included by nothing else.
+ * that IDR(s) calls.  idrs_core.h takes the guards (sqrt0, nonfinite) from here, also for the
+ * coupled model; included by nothing else.
  */
 #ifndef IEMIC_KRYLOV_INTERNAL_H
 #define IEMIC_KRYLOV_INTERNAL_H

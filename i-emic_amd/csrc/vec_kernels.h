@@ -1,6 +1,7 @@
 /*
  * vec_kernels.h -- the vector kernels that the Krylov units share: the block reduction, the
- * multi-dot pair, scale/copy, axpby and the linear combinations of up to 16 vectors.
+ * multi-dot pair, the IDR(s) shadow-space hash, scale/copy, axpby and the linear combinations
+ * of up to 16 vectors.
  * Included by spmv.hip, krylov.hip and idrs.hip (the ocean's vectors, default compiler flags)
  * and by coupled.hip and coupled_krylov.hip (the packed coupled vectors, built without
  * floating-point contraction).
@@ -72,6 +73,18 @@ static __global__ void k_mdot_final(const double* __restrict__ partial, int nb, 
     for (int b = threadIdx.x; b < nb; b += blockDim.x) s += partial[(int64_t)i * nb + b];
     double t = block_sum(s, sm);
     if (threadIdx.x == 0) out[i] = t;
+}
+
+/* ---- the IDR(s) shadow space -------------------------------------------------------------- */
+/* entry q of row g: uniform in [-1, 1], splitmix64 of (g, q) from the space's seed.  The callers
+ * (k_idr_random, k_cidr_random) map their threads to g */
+__device__ __forceinline__ double idr_shadow_entry(uint64_t g, int q, uint64_t seed)
+{
+    uint64_t z = 0x9E3779B97F4A7C15ull * (g * 16 + (uint64_t)q + 1) + seed;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return 2.0 * ((double)(z >> 11) * (1.0 / 9007199254740992.0)) - 1.0;
 }
 
 /* ---- BLAS-1 -------------------------------------------------------------------------- */

@@ -3,7 +3,8 @@ against CPU references, beyond "it converged".
 
 * cpl_prec through the test hook iemic_test_coupled_prec: the forward block Gauss-Seidel
   z_o = M_o^-1 r_o, z_a = M_a^-1 (r_a - C_ao z_o) against its composition in Python.
-* coupled_fgmres against fgmres_ref and coupled_idrs against idrs_ref (tests/krylov_ref.py) on
+* coupled_fgmres against fgmres_ref and IDR(s) (idrs_run of csrc/idrs_core.h over
+  CoupledSpace) against idrs_ref (tests/krylov_ref.py) on
   the assembled matrix [J_o C_oa; C_ao J_a]: the k-th iterate at tolerance 0, as
   tests/test_gpu_krylov.py and tests/test_gpu_idr.py do for the ocean's solvers.  This pins
   the reductions k_cdots / k_cfinal over KB = 512 blocks, k_cupdate, k_cupdate_m, k_cscale_dev,
@@ -446,10 +447,10 @@ def check_idr(s, ref, sdim, prec, angle, ks, label, **more):
 @pytest.mark.parametrize("prec", IDR_PRECS)
 @pytest.mark.parametrize("name,sdim", IDR_CASES)
 def test_coupled_idr_iterates(name, sdim, prec):
-    """coupled_idrs at k = 1, s, s + 1, s + 2, 2 s + 1, 2 s + 2 against idrs_ref with the shadow
+    """The coupled IDR(s) at k = 1, s, s + 1, s + 2, 2 s + 1, 2 s + 2 against idrs_ref with the shadow
     space of k_cidr_random in packed order; the default angle and 0.999, at which the
     reference reports the rule fired at both omega steps.  Preconditioner 2: M = the Python
-    composition of the block Gauss-Seidel (precon), so coupled_idrs runs through cpl_prec.
+    composition of the block Gauss-Seidel (precon), so the solve runs through cpl_prec.
     Steps kept and dropped: all six everywhere, except on coupled_natl8s with the
     preconditioner s = 4 (k = 1, 4, 5, 6 kept; 9, 10 dropped) and s = 8 (1, 8, 9, 10 kept; 17, 18
     dropped; right-hand side -F): see DROPPED.  In those two cases no second omega step is
@@ -472,7 +473,7 @@ def test_coupled_idr_iterates(name, sdim, prec):
 
 @pytest.mark.parametrize("name", GRIDS)
 def test_coupled_idr_residual_replacement(name):
-    """"IDR replace residuals" at tolerance 0, Preconditioner 0: coupled_idrs sets trueres after
+    """"IDR replace residuals" at tolerance 0, Preconditioner 0: idrs_run sets trueres after
     every update (normr > tolb / mp = 0) and, at an omega step, replaces r by b - A x when the
     norm it has just recomputed from the updated r is below ||b||.  In exact arithmetic the
     iterates do not change, and reorth counts the omega steps up to k at which the reference's
