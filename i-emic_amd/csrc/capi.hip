@@ -1096,6 +1096,66 @@ extern "C" int iemic_theta_newton_step(iemic_ctx* c, const iemic_krylov* opt, in
     return inf.solve.converged ? 0 : IEMIC_ENOCONV;
 }
 
+/* ---- linear stability analysis (eigs.hip): the JDQZInterface seam ------------------------ */
+/* Ocean::computeJacobian + the operator-side shift of JDQZInterface.H (alpha A - beta B) */
+extern "C" int iemic_shifted_jacobian(iemic_ctx* c, double sigma)
+{
+    CTX_CHECK(c);
+    int rc = shifted_jacobian(c, sigma);
+    if (rc) return rc;
+    DEV_SYNC(c);
+    return 0;
+}
+
+/* JDQZ's construction on the model (run_ocean.C:82-97) */
+extern "C" int iemic_eigs_begin(iemic_ctx* c, double sigma, int m, uint64_t seed, const iemic_krylov* opt)
+{
+    CTX_CHECK(c);
+    if (!opt) return IEMIC_EINVAL;
+    return eigs_begin(c, sigma, m, seed, opt);
+}
+
+/* one operator application of the eigen-iteration: applyMassMat, then the shifted solve */
+extern "C" int iemic_eigs_step(iemic_ctx* c, const iemic_krylov* opt, double* hcol, iemic_eigs_info* info)
+{
+    CTX_CHECK(c);
+    if (!opt || !hcol) return IEMIC_EINVAL;
+    return eigs_step(c, opt, hcol, info);
+}
+
+/* the eigenvectors JDQZ hands to Utils::saveEigenvectors (Continuation.H:1116-1120) */
+extern "C" int iemic_eigs_ritz(iemic_ctx* c, int j, int p, const double* Y, void** xvecs)
+{
+    CTX_CHECK(c);
+    if (!c->eg.active || j > c->eg.j + (c->eg.broke ? 0 : 1)) {
+        set_error("iemic_eigs_ritz: the run holds fewer than j basis vectors (iemic_eigs_begin, iemic_eigs_step)");
+        return IEMIC_ESTATE;
+    }
+    if (!xvecs || p < 1 || p > 16) {
+        set_error("iemic_eigs_ritz: needs 1 <= p <= 16 output vectors");
+        return IEMIC_EINVAL;
+    }
+    const int64_t o = NUN * c->sub.own0;
+    double* xs[16];
+    for (int q = 0; q < p; q++) xs[q] = xvecs[q] ? (double*)xvecs[q] + o : nullptr;
+    return eigs_ritz(c, c->eg.V.p + o, c->sub.nerows(), j, p, Y, xs, c->sub.nlrows());
+}
+
+/* the residual JDQZ reports per converged pair, measured on the operator itself */
+extern "C" int iemic_eigs_residual(iemic_ctx* c, double lam_re, double lam_im, double* x_re, double* x_im,
+                                   double out[2])
+{
+    CTX_CHECK(c);
+    return eigs_residual(c, lam_re, lam_im, x_re, x_im, out);
+}
+
+extern "C" int iemic_eigs_end(iemic_ctx* c)
+{
+    CTX_CHECK(c);
+    DEV_SYNC(c);
+    return eigs_end(c);
+}
+
 /* ---- device vectors: the Epetra_Vector algebra Continuation.H applies through Utils
  * (dot / norm / update over the solve map), on vectors in the ext layout; the owned rows
  * are one contiguous slab, reductions are summed over the ranks ------------------------ */

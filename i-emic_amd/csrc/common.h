@@ -342,6 +342,18 @@ struct Theta {
     DevBuf<double> Ft, b;            /* F_theta(x) and F_theta / dt / theta (the solve's rhs) */
 };
 
+/* A shift-invert Arnoldi run (eigs.hip): the basis of (J - sigma B)^-1 B and its work vectors,
+ * ext layout, allocated by eigs_begin and freed by eigs_end */
+struct Eigs {
+    int active = 0;                  /* a run is in progress (V, t, w current)            */
+    int m = 0, j = 0;                /* basis size of the run, steps taken                */
+    int broke = 0;                   /* the last step found an invariant subspace         */
+    double sigma = 0.0;
+    DevBuf<double> V;                /* (m + 1) x nerows                                  */
+    DevBuf<double> t, w;             /* B v_j (the solve's rhs) and the solve's output    */
+    DevBuf<double> lo;               /* 2 x nerows: the low parts of eigs_residual's products */
+};
+
 constexpr int RED_BLOCKS = 1024;     /* partial-sum blocks of the reductions            */
 constexpr int MAX_KRYLOV = 1000;     /* largest Krylov dimension                        */
 /* reduction rows (DCGS2: 2 per basis vector + 3 sums + beta, h_jj; the coefficient area
@@ -402,6 +414,7 @@ struct iemic_ctx {
     iemic::BlockGS gs;
     iemic::Krylov kr;
     iemic::Theta th;
+    iemic::Eigs eg;
     iemic::Geo geo() const;
     iemic_ctx() = default;
     iemic_ctx(const iemic_ctx&) = delete;
@@ -596,6 +609,22 @@ int theta_jacobian(iemic_ctx* c);
 /* state -= dx on the owned rows; *absmax: this rank's max |dx| (NaN propagates) */
 int theta_update(iemic_ctx* c, const double* dx, double* absmax);
 int theta_restore(iemic_ctx* c);
+/* eigs.hip: shift-invert Arnoldi for J x = lambda B x on the resident state */
+/* J(state) with -(sigma B) on the diagonal of the U, V, T and S rows (sigma = 0: J untouched) */
+int shifted_jacobian(iemic_ctx* c, double sigma);
+int eigs_begin(iemic_ctx* c, double sigma, int m, uint64_t seed, const iemic_krylov* opt);
+int eigs_step(iemic_ctx* c, const iemic_krylov* opt, double* hcol, iemic_eigs_info* info);
+int eigs_end(iemic_ctx* c);
+/* xs[q] = sum_i Y[i p + q] V_i (i < j, q < p <= 16) over N rows, one pass over V (stride ldv);
+ * Y: host, j x p row-major; V and xs point at the first row the launch covers */
+int eigs_ritz(iemic_ctx* c, const double* V, int64_t ldv, int j, int p, const double* Y, double* const* xs,
+              int64_t N);
+/* out2 = sum |a - mu B x|^2, sum |a|^2 over N rows (a, x complex; ai = xi = null: real),
+ * summed over the ranks; pointers at the first row */
+int eigs_residual_sums(iemic_ctx* c, const double* ar, const double* ai, const double* xr, const double* xi,
+                       const double* B, double mu_r, double mu_i, int64_t N, double* out2);
+/* the two norms of iemic_eigs_residual for ext vectors xr, xi (their halo rows are updated) */
+int eigs_residual(iemic_ctx* c, double lam_re, double lam_im, double* xr, double* xi, double* out2);
 /* prec.hip */
 int prec_compute(iemic_ctx* c, const iemic_krylov* opt);
 int prec_apply(iemic_ctx* c, const double* r, double* z);

@@ -234,6 +234,40 @@ class Ocean {
         return info;
     }
 
+    /* ---- linear stability analysis: the calls a JDQZInterface-shaped eigen-solver makes
+     * (src/utils/JDQZInterface.H); the Hessenberg eigen-decomposition is the caller's
+     * (INTEGRATION.md shows it with LAPACKE_dhseqr / dtrevc) ------------------------- */
+    /* J - sigma B at the state: solve, applyMatrix and buildPreconditioner then act on it;
+     * computeJacobian restores J */
+    void shiftedJacobian(double sigma) { check(iemic_shifted_jacobian(ctx_, sigma), "shiftedJacobian"); }
+    /* a shift-invert Arnoldi run on (J - sigma B)^-1 B: at most m <= IEMIC_EIGS_MAX_M steps */
+    void eigsBegin(double sigma, int m, uint64_t seed = 1)
+    {
+        check(iemic_eigs_begin(ctx_, sigma, m, seed, &krylov_), "eigsBegin");
+        recompPrec_ = false;
+    }
+    /* one step: hcol receives column info.step of the Hessenberg matrix (step + 2 doubles); an
+     * inner solve that missed its tolerance shows in info.solve.converged */
+    iemic_eigs_info eigsStep(double* hcol)
+    {
+        iemic_eigs_info info{};
+        const int rc = iemic_eigs_step(ctx_, &krylov_, hcol, &info);
+        if (rc != IEMIC_ENOCONV) check(rc, "eigsStep");
+        lastSolve_ = info.solve;
+        return info;
+    }
+    /* xvecs[q] = sum_i Y[i p + q] v_i, i < j: p device vectors from iemic_vec_alloc */
+    void eigsRitz(int j, int p, const double* Y, void** xvecs)
+    {
+        check(iemic_eigs_ritz(ctx_, j, p, Y, xvecs), "eigsRitz");
+    }
+    /* out = ||(J - sigma B) x - (lambda - sigma) B x||, ||(J - sigma B) x|| */
+    void eigsResidual(double lamRe, double lamIm, double* xRe, double* xIm, double out[2])
+    {
+        check(iemic_eigs_residual(ctx_, lamRe, lamIm, xRe, xIm, out), "eigsResidual");
+    }
+    void eigsEnd() { check(iemic_eigs_end(ctx_), "eigsEnd"); }
+
     size_t nrows() const { return N_; }
     iemic_ctx* handle() { return ctx_; }
 

@@ -4,7 +4,8 @@
  * preconditioner (coupled.hip) for tests/test_gpu_coupled_krylov.py, and the DCGS2 update pass
  * (krylov.hip) for tests/test_dcgs_fused_coef.py, and the T/S multigrid's plan, levels and
  * fusion switch (iemic_test_ts_mg_plan, iemic_test_ts_mg_level, iemic_test_ts_mg_nofuse;
- * ts_mg.hip, ts_mg_setup.hip) for tests/test_gpu_ts_mg.py.  They are exported from the
+ * ts_mg.hip, ts_mg_setup.hip) for tests/test_gpu_ts_mg.py, and the Ritz-vector and residual
+ * kernels of the stability analysis (eigs.hip) for tests/test_gpu_eigs.py.  They are exported from the
  * device library but are NOT part of its public ABI (include/iemic.h, IEMIC_ABI_VERSION):
  * tests/dense_hooks.py binds them.  All pointers are host pointers; every hook runs on the
  * context's stream, owns its device buffers and returns the usual IEMIC_* codes.
@@ -85,6 +86,17 @@ int iemic_test_ts_mg_level(iemic_ctx* ctx, int q, double* off, double* diag, dou
 
 /* on != 0: no level is visited by the fused launches (k_mg_dn / k_mg_up) until it is cleared */
 int iemic_test_ts_mg_nofuse(iemic_ctx* ctx, int on);
+
+/* k_eig_ritz (eigs.hip) on an arbitrary basis: V (j x ldv, ldv >= N), Y (j x p row-major),
+ * X (p x N) = the p combinations sum_i Y[i][q] V_i over the first N entries of every row; the
+ * device copy of X starts as NaN bit patterns. */
+int iemic_test_eig_ritz(iemic_ctx* ctx, int j, int p, int64_t N, int64_t ldv, const double* V, const double* Y,
+                        double* X);
+
+/* k_eig_residual and its second stage (eigs.hip) on host data of length N: out2 = sum |a - mu B
+ * x|^2, sum |a|^2 with a = ar + i ai, x = xr + i xi, mu = mu_r + i mu_i; ai = xi = NULL: real. */
+int iemic_test_eig_residual(iemic_ctx* ctx, int64_t N, const double* ar, const double* ai, const double* xr,
+                            const double* xi, const double* B, double mu_r, double mu_i, double* out2);
 
 #ifdef __cplusplus
 }

@@ -312,3 +312,39 @@ extern "C" int iemic_test_ts_mg_nofuse(iemic_ctx* c, int on)
     c->gs.mg.nofuse = on != 0;
     return 0;
 }
+
+extern "C" int iemic_test_eig_ritz(iemic_ctx* c, int j, int p, int64_t N, int64_t ldv, const double* V,
+                                   const double* Y, double* X)
+{
+    if (!c || !V || !Y || !X) return bad("null argument");
+    if (j < 1 || j > IEMIC_EIGS_MAX_M || p < 1 || p > 16 || N < 1 || N > (1 << 24) || ldv < N)
+        return bad("Ritz shape out of range");
+    if (hipSetDevice(c->device) != hipSuccess) return IEMIC_EDEVICE;
+    DevBuf<double> vd, xd;
+    if (vd.alloc((size_t)j * ldv) || xd.alloc((size_t)p * N)) return IEMIC_ENOMEM;
+    int rc;
+    if ((rc = h2d(c, vd.p, V, sizeof(double) * j * ldv))) return rc;
+    HIP_OK(hipMemsetAsync(xd.p, 0xff, sizeof(double) * p * N, c->stream));
+    double* xs[16] = {};
+    for (int q = 0; q < p; q++) xs[q] = xd.p + (int64_t)q * N;
+    if ((rc = eigs_ritz(c, vd.p, ldv, j, p, Y, xs, N))) return rc;
+    return d2h(c, X, xd.p, sizeof(double) * p * N);
+}
+
+extern "C" int iemic_test_eig_residual(iemic_ctx* c, int64_t N, const double* ar, const double* ai, const double* xr,
+                                       const double* xi, const double* B, double mu_r, double mu_i, double* out2)
+{
+    if (!c || !ar || !xr || !B || !out2 || (ai == nullptr) != (xi == nullptr)) return bad("null argument");
+    if (N < 1 || N > (1 << 24)) return bad("residual length out of range");
+    if (c->sub.nranks != 1) return bad("a single-rank context is needed");
+    if (hipSetDevice(c->device) != hipSuccess) return IEMIC_EDEVICE;
+    const int nvec = ai ? 5 : 3;
+    DevBuf<double> d;
+    if (d.alloc((size_t)nvec * N)) return IEMIC_ENOMEM;
+    const double* src[5] = {ar, xr, B, ai, xi};
+    int rc;
+    for (int q = 0; q < nvec; q++)
+        if ((rc = h2d(c, d.p + (int64_t)q * N, src[q], sizeof(double) * N))) return rc;
+    return eigs_residual_sums(c, d.p, ai ? d.p + 3 * N : nullptr, d.p + N, ai ? d.p + 4 * N : nullptr, d.p + 2 * N,
+                              mu_r, mu_i, N, out2);
+}

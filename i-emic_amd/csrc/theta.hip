@@ -15,18 +15,9 @@
 #include <algorithm>
 
 #include "common.h"
+#include "mass_slots.h"
 
 namespace iemic {
-
-/* the diagonal slots of the rows with a mass-matrix entry (W and P: B = 0), from the slot table */
-constexpr int THETA_ROWS = 4;
-constexpr int THETA_VAR[THETA_ROWS] = {UU, VV, TT, SS};
-constexpr int THETA_SLOT[THETA_ROWS] = {
-    slot_of(UU, pos_of(0, 0, 0), UU), slot_of(VV, pos_of(0, 0, 0), VV),
-    slot_of(TT, pos_of(0, 0, 0), TT), slot_of(SS, pos_of(0, 0, 0), SS)};
-static_assert(THETA_SLOT[0] == ROW_BEGIN[UU] && THETA_SLOT[1] == ROW_BEGIN[VV] &&
-                  THETA_SLOT[2] == ROW_BEGIN[TT] && THETA_SLOT[3] == ROW_BEGIN[SS],
-              "every row's first slot is its diagonal");
 
 /* val[diagonal slot of row v][lc] += -B / dt / theta for v = U, V, T, S (blockIdx.y) of every
  * assembled cell: lanes along the cells, so each plane is written in contiguous 512-byte

@@ -16,7 +16,7 @@ PKG_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(PKG_DIR, "lib", os.environ.get("IEMIC_LIB", "libiemic_amd.so"))
 
 IEMIC_ENODEV = -19
-ABI_VERSION = 8             # IEMIC_ABI_VERSION of include/iemic.h this binding mirrors
+ABI_VERSION = 9             # IEMIC_ABI_VERSION of include/iemic.h this binding mirrors
 IEMIC_ENOCONV = 1           # iemic_newton_step: applied, but the solve missed its tolerance
 
 
@@ -88,6 +88,16 @@ class ThetaInfo(C.Structure):
     _fields_ = [("norm_f0", C.c_double), ("norm_f1", C.c_double), ("norm_dx", C.c_double),
                 ("solve", SolveInfo), ("t_jac_ms", C.c_double), ("t_rhs_ms", C.c_double),
                 ("t_prec_ms", C.c_double), ("t_solve_ms", C.c_double), ("t_total_ms", C.c_double)]
+
+
+class EigsInfo(C.Structure):
+    """iemic_eigs_info: one shift-invert Arnoldi step."""
+    _fields_ = [("step", C.c_int), ("breakdown", C.c_int), ("solve", SolveInfo),
+                ("t_solve_ms", C.c_double), ("t_orth_ms", C.c_double), ("t_scale_ms", C.c_double),
+                ("t_total_ms", C.c_double)]
+
+
+EIGS_MAX_M = 64             # IEMIC_EIGS_MAX_M
 
 
 def grid_from_config(cfg, device: int = 0, analyze_jacobian: bool = True) -> Grid:
@@ -170,6 +180,12 @@ def lib():
         "iemic_theta_jacobian": (C.c_int, [vp]),
         "iemic_theta_restore": (C.c_int, [vp]),
         "iemic_theta_newton_step": (C.c_int, [vp, P(Krylov), C.c_int, P(ThetaInfo)]),
+        "iemic_shifted_jacobian": (C.c_int, [vp, C.c_double]),
+        "iemic_eigs_begin": (C.c_int, [vp, C.c_double, C.c_int, C.c_uint64, P(Krylov)]),
+        "iemic_eigs_step": (C.c_int, [vp, P(Krylov), PD, P(EigsInfo)]),
+        "iemic_eigs_ritz": (C.c_int, [vp, C.c_int, C.c_int, PD, P(vp)]),
+        "iemic_eigs_residual": (C.c_int, [vp, C.c_double, C.c_double, vp, vp, PD]),
+        "iemic_eigs_end": (C.c_int, [vp]),
         "iemic_vec_alloc": (C.c_int, [vp, P(vp)]),
         "iemic_vec_free": (C.c_int, [vp, vp]),
         "iemic_vec_update": (C.c_int, [vp, C.c_double, vp, C.c_double, vp, C.c_double, vp]),
@@ -249,7 +265,9 @@ EXPORTED = ("iemic_abi_version", "iemic_create", "iemic_create_dist", "iemic_com
             "iemic_jacobian", "iemic_rhs", "iemic_diag_b", "iemic_export_csr", "iemic_spmv",
             "iemic_spmv_dev", "iemic_prec_compute", "iemic_prec_apply", "iemic_solve",
             "iemic_solve_dev", "iemic_newton_step", "iemic_theta_init_step", "iemic_theta_rhs",
-            "iemic_theta_jacobian", "iemic_theta_restore", "iemic_theta_newton_step", "iemic_vec_alloc", "iemic_vec_free",
+            "iemic_theta_jacobian", "iemic_theta_restore", "iemic_theta_newton_step",
+            "iemic_shifted_jacobian", "iemic_eigs_begin", "iemic_eigs_step", "iemic_eigs_ritz",
+            "iemic_eigs_residual", "iemic_eigs_end", "iemic_vec_alloc", "iemic_vec_free",
             "iemic_vec_update", "iemic_vec_dot", "iemic_vec_norm_inf", "iemic_vec_from_ref",
             "iemic_vec_to_ref", "iemic_state_vec", "iemic_rhs_vec", "iemic_time_spmv", "iemic_time_spmv_cold", "iemic_time_prec",
             "iemic_time_prec_parts",

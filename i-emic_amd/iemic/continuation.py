@@ -16,8 +16,10 @@ device vectors in HBM whose dots and norms are summed over its ranks, so the sta
 dF/dpar and the corrector's two solutions never leave the GPU and the same driver runs on
 every rank of a decomposed model; other models (host numpy vectors in the reference row
 order) get ``HostOps``.  The ops are functional (every result is a new vector), which is
-how the code below reads Continuation.H's Epetra Update calls.  Eigenvalue analysis (JDQZ)
-and user monitors are not restated.
+how the code below reads Continuation.H's Epetra Update calls.  Eigenvalue analysis runs
+through the ``eigen_solver`` attribute (the reference's setEigenSolver, Continuation.H:1097-1103;
+``iemic.eigs.EigenSolver`` for the GPU Ocean) at the reference's two points; user monitors are
+not restated.
 """
 from __future__ import annotations
 
@@ -41,6 +43,8 @@ DEFAULTS = {
     "post processing": "at every point", "predictor bound": 1e3,
     # Continuation.H:1336-1338
     "enable backtracking": False, "backtracking steps": 0, "backtracking increase": 0.0,
+    # Continuation.H:1349: 'N' none, 'P' at every converged point, 'E' at every destination
+    "eigenvalue analysis": "N",
 }
 
 
@@ -113,6 +117,7 @@ class StepRecord:
     norm_x: float
     norm_f: float
     newton_iters: int
+    eig: object = None          # the eigen-solver's result when it ran at this step
 
 
 class Continuation:
@@ -152,6 +157,11 @@ class Continuation:
         self.numBackTrackingSteps = int(p["backtracking steps"])
         self.backTrackIncrease = float(p["backtracking increase"])
         self.backTrack = 0
+        self.eigenvalueAnalysis = p["eigenvalue analysis"]
+        if self.eigenvalueAnalysis not in ("N", "P", "E"):
+            raise ValueError(f"eigenvalue analysis = {self.eigenvalueAnalysis!r}: expected 'N', 'P' or 'E'")
+        self.eigen_solver = None        # setEigenSolver: an object with solve() (iemic.eigs.EigenSolver)
+        self._eig = None
         self.destinations = []
         for i in range(999):
             d = p.get(f"destination {i}")
@@ -413,6 +423,11 @@ class Continuation:
             self.ds = -f1 * self.ds / (f1 - f0)
             self.createTangent("S")
         if self.secant and abs(f1) < self.destTol:
+            # :912-914: eigenvalues at every converged destination, into the step just recorded
+            if self.eigenvalueAnalysis == "E":
+                self.eigenSolver()
+                if self.history:
+                    self.history[-1].eig = self._eig
             self.secant = False
             self.ds = self.dsStart
             self.fixStepSize = True
@@ -423,14 +438,33 @@ class Continuation:
             else:
                 self.signMonitor[0] = _sgn(self.par - self.destinations[0])
 
+    # ---- 1097-1131 -------------------------------------------------------------------
+    def setEigenSolver(self, solver) -> None:
+        self.eigen_solver = solver
+
+    def eigenSolver(self) -> None:
+        """Continuation::eigenSolver: the solver's result is kept for the step's StepRecord (the
+        reference saves the eigenvectors to ev_step_<step>); without a solver set it warns."""
+        if self.eigenvalueAnalysis == "N":
+            return
+        if self.eigen_solver is None:
+            import warnings
+            warnings.warn("Continuation: eigen solver not set")
+            return
+        self._eig = self.eigen_solver.solve()
+
     # ---- 230-298 ---------------------------------------------------------------------
     def step(self) -> int:
+        self._eig = None
         self.model.preProcess()
         if self.eulerPredictor():
             return 1
         if self.newtonCorrector():
             return 1
         self.createTangent(self.tangentType)
+        # :278-280: eigenvalues at every converged step, between createTangent and postProcess
+        if self.eigenvalueAnalysis == "P":
+            self.eigenSolver()
         if self.postProcessMode == "at every point":
             self.model.postProcess()
         return 0
@@ -447,7 +481,7 @@ class Continuation:
                 continue
             self.history.append(StepRecord(self.step_, self.par, self.ds,
                                            self._norm(self.ops.state()),
-                                           self.normRHStest, self.newtonIter))
+                                           self.normRHStest, self.newtonIter, self._eig))
             self.detect()
             self.adjustStep()
         if self.abortFlag:

@@ -691,6 +691,34 @@ class Ocean:
             self.solve_hook(info.solve)
         return info
 
+    # ---- linear stability analysis (the JDQZInterface seam; iemic.eigs) -----------------
+    def shiftedJacobian(self, sigma: float) -> None:
+        """J - sigma B at the current state (J is assembled first); exportCSR, applyMatrix,
+        buildPreconditioner and solve then act on it, diagB still returns B and
+        computeJacobian restores J.  A non-finite sigma raises IemicError by name."""
+        check(lib().iemic_shifted_jacobian(self._h, float(sigma)), "iemic_shifted_jacobian")
+
+    def eigs(self, k: int = 6, sigma: float = 0.0, m: int = 40, tol: float = 1e-8, seed: int = 1):
+        """The k eigenvalues of J x = lambda B x nearest the real shift sigma at the current
+        state, with eigenvectors, by unrestarted shift-invert Arnoldi of at most m steps
+        (m <= 64) on (J - sigma B)^-1 B -> iemic.eigs.EigResult.
+
+        After every step from k on the leading Hessenberg block is decomposed
+        (numpy.linalg.eig); the run stops when the k Ritz pairs of largest |theta| all have
+        the estimate |h_{j+1,j}| |e_j^T y| / |theta| <= tol, at a breakdown (an invariant
+        Krylov space: every pair exact) or after m steps.  A conjugate pair is never split:
+        k grows by one when the k-th and (k+1)-th are a pair.  Nothing is dropped: a wanted
+        pair that missed tol comes back with converged=False.  The true residual of every
+        pair is measured on the device.  A perturbation grows like exp(lambda t), so the
+        state is stable iff every finite lambda has a negative real part.
+
+        The inner solves use this Ocean's solver_params; keep "FGMRES tolerance" at least 100
+        times tighter than tol, since the inexact solve limits the attainable residual.  The
+        Jacobian is left shifted and the preconditioner is that of J - sigma B: the next
+        computeJacobian restores J and the next solve refactors."""
+        from . import eigs as _eigs
+        return _eigs.eigs(self, k=k, sigma=sigma, m=m, tol=tol, seed=seed)
+
     # ---- inspection -----------------------------------------------------------------
     def exportCSR(self):
         nnz = lib().iemic_graph_nnz(self._h)

@@ -45,9 +45,10 @@ extern "C" {
 
 /* Version of this header's structs and entry points.  Bumped whenever a struct changes
  * size or meaning (5: iemic_solve_info gained `safeguard` in round 4, the device vector
- * algebra of round 5; 7: surface fluxes and inserted forcing fields; 8: the theta time stepper); a caller built against another header must refuse to run:
+ * algebra of round 5; 7: surface fluxes and inserted forcing fields; 8: the theta time stepper;
+ * 9: linear stability analysis); a caller built against another header must refuse to run:
  *   if (iemic_abi_version() != IEMIC_ABI_VERSION) abort(); */
-#define IEMIC_ABI_VERSION 8
+#define IEMIC_ABI_VERSION 9
 int iemic_abi_version(void);
 
 typedef struct iemic_ctx iemic_ctx;
@@ -409,6 +410,61 @@ typedef struct {
 } iemic_theta_info;
 int iemic_theta_newton_step(iemic_ctx* ctx, const iemic_krylov* opt, int refactor,
                             iemic_theta_info* info);
+
+/* ---- linear stability of the state: J x = lambda B x by shift-invert Arnoldi -----------
+ * The seam is the generalised eigenvalue solver the reference's drivers build on
+ * applyMatrix / applyMassMat / applyPrecon (src/utils/JDQZInterface.H; run_ocean.C:82-97)
+ * and hand to Continuation::setEigenSolver (Continuation.H:1097-1103, run at :278-280 and
+ * :912-914).  JDQZ itself is an external library, so this is an original solver behind that
+ * seam: Arnoldi on (J - sigma B)^-1 B with a real shift sigma, whose eigenvalues
+ * theta = 1 / (lambda - sigma) are largest for the lambda nearest sigma; the infinite
+ * eigenvalues (B is singular) map to theta = 0.  A perturbation grows like exp(lambda t): the
+ * state is stable iff every finite lambda has a negative real part.  The library links no
+ * LAPACK: the eigen-decomposition of the small Hessenberg matrix is the caller's
+ * (iemic/eigs.py uses numpy). */
+/* Ocean::computeJacobian followed by the shift JDQZInterface applies operator-side
+ * (alpha A - beta B): J - sigma B at the current state; J is assembled first.
+ * iemic_export_csr, iemic_spmv, iemic_prec_compute and iemic_solve then act on J - sigma B,
+ * iemic_diag_b still returns B, and the next iemic_jacobian restores J.  sigma = 0 leaves
+ * every bit of J.  A NaN or infinite sigma is refused with IEMIC_EINVAL. */
+int iemic_shifted_jacobian(iemic_ctx* ctx, double sigma);
+#define IEMIC_EIGS_MAX_M 64      /* largest Arnoldi basis of one run */
+typedef struct {
+    int step;                    /* index j of the column this step produced (0-based)  */
+    int breakdown;               /* h_{j+1,j} <= 1e-14 ||column||: the Krylov space is   */
+                                 /* invariant, every Ritz pair is exact, the run is over */
+    iemic_solve_info solve;      /* the inner solve (J - sigma B) w = B v_j              */
+    double t_solve_ms, t_orth_ms, t_scale_ms, t_total_ms;
+} iemic_eigs_info;
+/* Starts a run (JDQZ's constructor + the first applyPrecon set-up): the shifted Jacobian at the
+ * current state, its preconditioner (opt->prec > 0), m + 1 basis vectors and two work vectors,
+ * and the start vector v_0: a uniform deterministic fill from `seed`, indexed by the global
+ * row (the same on any number of ranks), normalised.  m < 1, m > IEMIC_EIGS_MAX_M and a
+ * non-finite sigma are refused with IEMIC_EINVAL before anything is launched; IEMIC_ENOMEM when
+ * the basis does not fit.  A run in progress is replaced. */
+int iemic_eigs_begin(iemic_ctx* ctx, double sigma, int m, uint64_t seed, const iemic_krylov* opt);
+/* One Arnoldi step j (applyMassMat, then the shifted solve in applyPrecon's place):
+ * w = (J - sigma B)^-1 (B v_j) by the context's solver on the run's preconditioner, two
+ * classical Gram-Schmidt passes against v_0..v_j, v_{j+1} = w / ||w||.  hcol (j + 2 doubles):
+ * column j of the Hessenberg matrix, h_{0..j,j} and h_{j+1,j}.  IEMIC_ESTATE before
+ * iemic_eigs_begin, after m steps or after a breakdown; IEMIC_ERANGE for a non-finite column;
+ * IEMIC_ENOCONV when the inner solve missed its tolerance (the step is applied). */
+int iemic_eigs_step(iemic_ctx* ctx, const iemic_krylov* opt, double* hcol, iemic_eigs_info* info);
+/* The Ritz vectors X = [v_0 .. v_{j-1}] Y in one pass over the basis: Y is j x p, row-major,
+ * host (columns alternating the real and imaginary parts of the wanted pairs), 1 <= p <= 16;
+ * xvecs: p device vectors from iemic_vec_alloc, overwritten on the owned rows. */
+int iemic_eigs_ritz(iemic_ctx* ctx, int j, int p, const double* Y, void** xvecs);
+/* out[0] = ||(J - sigma B) x - (lambda - sigma) B x||, out[1] = ||(J - sigma B) x|| for the
+ * pair lambda = lam_re + i lam_im, x = x_re + i x_im (device vectors; x_im NULL for a real
+ * pair), with the run's sigma on the run's shifted Jacobian; sums over the ranks, bit-wise
+ * reproducible.  The difference is formed in double-double, so a residual ten orders below
+ * its two terms is still accurate to well under 1e-6 of itself; the first call allocates two
+ * more vectors (freed by iemic_eigs_end; IEMIC_ENOMEM).  IEMIC_ESTATE outside a run. */
+int iemic_eigs_residual(iemic_ctx* ctx, double lam_re, double lam_im, double* x_re, double* x_im,
+                        double out[2]);
+/* Frees the basis.  The context's Jacobian stays J - sigma B (as after iemic_theta_jacobian):
+ * the next iemic_jacobian restores J. */
+int iemic_eigs_end(iemic_ctx* ctx);
 
 /* ---- profiling helpers (bench): time n launches of the SpMV kernel with HIP events
  * on the stream it runs on; returns mean kernel milliseconds. */
