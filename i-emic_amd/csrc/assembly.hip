@@ -286,9 +286,9 @@ int assemble_rhs(iemic_ctx* c, const double* x_dev, double* F_dev)
         /* the integral condition couples every S unknown: owned partial dot, a sum over the
          * ranks, and the owning rank writes the entry */
         const int nb = 256;
-        const int64_t o = NUN * c->sub.own0;
-        hipLaunchKernelGGL(k_dot_partial, dim3(nb), dim3(256), 0, c->stream, c->d_intc.p + o,
-                           x_dev + o, c->sub.nlrows(), c->d_red.p);
+        const Owned w = owned(c);
+        hipLaunchKernelGGL(k_dot_partial, dim3(nb), dim3(256), 0, c->stream, c->d_intc.p + w.o,
+                           x_dev + w.o, w.n, c->d_red.p);
         hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(64), 0, c->stream, c->d_red.p, nb,
                            c->d_red.p + nb);
         int rc = allreduce_sum(c, c->d_red.p + nb, 1);
@@ -309,8 +309,8 @@ int intcond_correction(iemic_ctx* c, const double* x_dev)
         return 0;
     }
     const int nb = 256;
-    const int64_t o = NUN * c->sub.own0;
-    hipLaunchKernelGGL(k_dot_partial, dim3(nb), dim3(256), 0, c->stream, c->d_intc.p + o, x_dev + o, c->sub.nlrows(),
+    const Owned w = owned(c);
+    hipLaunchKernelGGL(k_dot_partial, dim3(nb), dim3(256), 0, c->stream, c->d_intc.p + w.o, x_dev + w.o, w.n,
                        c->d_red.p);
     hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(64), 0, c->stream, c->d_red.p, nb, c->d_red.p + nb);
     int rc = allreduce_sum(c, c->d_red.p + nb, 1);

@@ -355,6 +355,21 @@ struct Eigs {
 };
 
 constexpr int RED_BLOCKS = 1024;     /* partial-sum blocks of the reductions            */
+/* the larger of a running maximum v and the next value a; a NaN on either side wins (it is
+ * taken, and nothing is larger than it afterwards) */
+__host__ __device__ inline double nanmax(double v, double a) { return (a > v || a != a) ? a : v; }
+/* nanmax of v over a block of 256 threads, in thread 0 (sm: 4 doubles of LDS) */
+__device__ inline double block_nanmax(double v, double* sm)
+{
+    for (int o = 32; o > 0; o >>= 1) v = nanmax(v, __shfl_down(v, o, 64));
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        v = sm[0];
+        for (int w = 1; w < 4; w++) v = nanmax(v, sm[w]);
+    }
+    return v;
+}
 constexpr int MAX_KRYLOV = 1000;     /* largest Krylov dimension                        */
 /* reduction rows (DCGS2: 2 per basis vector + 3 sums + beta, h_jj; the coefficient area
  * d_hbuf[RED_ROWS..] holds 2 per basis vector and 1/beta, gamma at DCGS_SCAL) */
@@ -450,6 +465,33 @@ inline int d2h(iemic_ctx* c, void* dst, const void* src, size_t bytes)
     HIP_OK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
     DEV_SYNC(c);
     return 0;
+}
+/* nanmax of d_part[0 .. nb), the block maxima a kernel left there, on the host */
+inline int part_nanmax(iemic_ctx* c, int nb, double* mx)
+{
+    std::vector<double> part(nb);
+    const int rc = d2h(c, part.data(), c->d_part.p, sizeof(double) * nb);
+    if (rc) return rc;
+    *mx = 0.0;
+    for (double v : part) *mx = nanmax(*mx, v);
+    return 0;
+}
+/* blocks of 256 threads for an element-wise kernel over N rows (grid-stride beyond 2048) */
+inline unsigned grid_for(int64_t N)
+{
+    int64_t b = (N + 255) / 256;
+    return (unsigned)std::min<int64_t>(b, 2048);
+}
+/* the owned slab of an ext vector, rows [o, o + n), and the grid of an element-wise launch
+ * over it.  (Reductions into d_part take their own grids, capped by RED_BLOCKS.) */
+struct Owned {
+    int64_t o, n;
+    unsigned grid;
+};
+inline Owned owned(const iemic_ctx* c)
+{
+    const int64_t n = c->sub.nlrows();
+    return {NUN * c->sub.own0, n, grid_for(n)};
 }
 /* p[0 .. n) = 0 by a kernel of the library.  Used instead of hipMemsetAsync on the solve
  * path: the HIP runtime dispatches a memset as its own blit kernel, and rocprofv3's kernel
@@ -631,6 +673,8 @@ int prec_apply(iemic_ctx* c, const double* r, double* z);
 /* the block GS apply from a compressed input (6 rows per ActiveSet::act cell, zero land rows) */
 /* staged: rc is already in the block GS's planar right-hand side (k_dcgs_update) */
 int gs_apply_c(iemic_ctx* c, const double* rc, double* z, bool staged = false);
+/* prec_gs.hip: GPU microseconds of the block GS apply's four parts (one rank) */
+int gs_time_parts(iemic_ctx* c, int nrep, double* us);
 /* y = J x written compressed (rows of the active cells only; x full, halo current) */
 int spmv_kernel_c(iemic_ctx* c, const double* x, double* yc, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 }  // namespace iemic

@@ -360,7 +360,8 @@ int eigs_begin(iemic_ctx* c, double sigma, int m, uint64_t seed, const iemic_kry
     int rc = shifted_jacobian(c, sigma);
     if (rc) return rc;
     if (opt->prec > 0 && (rc = prec_compute(c, opt))) return rc;
-    const int64_t NE = c->sub.nerows(), o = NUN * c->sub.own0, NL = c->sub.nlrows();
+    const int64_t NE = c->sub.nerows();
+    const auto [o, NL, G] = owned(c);
     if (eg.V.alloc((size_t)(m + 1) * NE) || eg.t.alloc(NE) || eg.w.alloc(NE)) {
         eigs_end(c);
         set_error("iemic_eigs_begin: out of device memory for the Arnoldi basis");
@@ -382,7 +383,7 @@ int eigs_begin(iemic_ctx* c, double sigma, int m, uint64_t seed, const iemic_kry
         set_error("iemic_eigs_begin: the start vector has no finite positive norm");
         return IEMIC_ERANGE;
     }
-    hipLaunchKernelGGL(k_eig_scale_bmul, dim3(grid_for(NL)), dim3(256), 0, c->stream, eg.w.p + o, c->d_B.p + o,
+    hipLaunchKernelGGL(k_eig_scale_bmul, dim3(G), dim3(256), 0, c->stream, eg.w.p + o, c->d_B.p + o,
                        1.0 / nrm, eg.V.p + o, eg.t.p + o, NL);
     HIP_OK(hipGetLastError());
     eg.sigma = sigma;
@@ -426,7 +427,8 @@ int eigs_step(iemic_ctx* c, const iemic_krylov* opt, double* hcol, iemic_eigs_in
     iemic_eigs_info inf{};
     const auto T0 = std::chrono::steady_clock::now();
     const int j = eg.j;
-    const int64_t NE = c->sub.nerows(), o = NUN * c->sub.own0, NL = c->sub.nlrows();
+    const int64_t NE = c->sub.nerows();
+    const auto [o, NL, G] = owned(c);
     inf.step = j;
     auto t0 = std::chrono::steady_clock::now();
     int rc = krylov_solve(c, eg.t.p, eg.w.p, opt, &inf.solve);
@@ -464,7 +466,7 @@ int eigs_step(iemic_ctx* c, const iemic_krylov* opt, double* hcol, iemic_eigs_in
     if (hn <= 1e-14 * std::sqrt(col2)) {
         inf.breakdown = eg.broke = 1;
     } else {
-        hipLaunchKernelGGL(k_eig_scale_bmul, dim3(grid_for(NL)), dim3(256), 0, c->stream, eg.w.p + o, c->d_B.p + o,
+        hipLaunchKernelGGL(k_eig_scale_bmul, dim3(G), dim3(256), 0, c->stream, eg.w.p + o, c->d_B.p + o,
                            1.0 / hn, eg.V.p + (int64_t)(j + 1) * NE + o, eg.t.p + o, NL);
         HIP_OK(hipGetLastError());
         DEV_SYNC(c);
@@ -552,7 +554,8 @@ int eigs_residual(iemic_ctx* c, double lam_re, double lam_im, double* xr, double
         set_error("iemic_eigs_residual: no Jacobian assembled");
         return IEMIC_ESTATE;
     }
-    const int64_t NE = c->sub.nerows(), o = NUN * c->sub.own0, nloc = c->sub.nloc;
+    const int64_t NE = c->sub.nerows(), nloc = c->sub.nloc;
+    const auto [o, NL, G] = owned(c);
     if (eg.lo.reserve((size_t)2 * NE)) {
         set_error("iemic_eigs_residual: out of device memory for the products' low parts");
         return IEMIC_ENOMEM;
@@ -573,7 +576,7 @@ int eigs_residual(iemic_ctx* c, double lam_re, double lam_im, double* xr, double
          * parts each), into the owner's entry */
         double* d4 = c->d_hbuf.p + 2;
         hipLaunchKernelGGL(k_eig_intcond_dd, dim3(2), dim3(256), 0, c->stream, c->d_intc.p + o, xr + o,
-                           xi ? xi + o : nullptr, c->sub.nlrows(), d4);
+                           xi ? xi + o : nullptr, NL, d4);
         HIP_OK(hipGetLastError());
         if ((rc = allreduce_sum(c, d4, 4))) return rc;
         if (c->rowintcon >= 0) {
@@ -589,7 +592,7 @@ int eigs_residual(iemic_ctx* c, double lam_re, double lam_im, double* xr, double
     double s[2];
     rc = residual_sums(c, ResidualIn{ahr + o, xi ? ahi + o : nullptr, alr + o, xi ? ali + o : nullptr, xr + o,
                                      xi ? xi + o : nullptr, c->d_B.p + o, mh, ml, lam_im},
-                       c->sub.nlrows(), s);
+                       NL, s);
     if (rc) return rc;
     out2[0] = sqrt0(s[0]);
     out2[1] = sqrt0(s[1]);

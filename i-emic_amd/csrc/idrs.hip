@@ -85,7 +85,8 @@ int idrs(iemic_ctx* c, const double* b, double* x, const iemic_krylov* opt, iemi
 {
     iemic_solve_info inf{};
     auto T0 = std::chrono::steady_clock::now();
-    OceanSpace sp{c, opt->prec > 0, c->sub.nerows(), NUN * c->sub.own0, c->sub.nlrows(), grid_for(c->sub.nlrows()), c->stream};
+    const Owned w = owned(c);
+    OceanSpace sp{c, opt->prec > 0, c->sub.nerows(), w.o, w.n, w.grid, c->stream};
     int rc = dev_zero(c, x, sp.ld);
     if (rc) return rc;
     const double normb = sqrt0(dot(c, b, b, 0));

@@ -457,14 +457,14 @@ int mdot_host(iemic_ctx* c, const double* V, int64_t ldv, int nvec, const double
 /* a . b over the owned rows of two ext vectors, summed over the ranks (error code) */
 int dot_owned(iemic_ctx* c, const double* a, const double* b, double* out)
 {
-    const int64_t o = NUN * c->sub.own0;
+    const int64_t o = owned(c).o;
     return mdot_host(c, a + o, 0, 1, b + o, out);
 }
 
 /* a . b over the owned rows of two ext vectors, summed over the ranks */
 double dot(iemic_ctx* c, const double* a, const double* b, int64_t)
 {
-    const int64_t o = NUN * c->sub.own0;
+    const int64_t o = owned(c).o;
     double r = 0.0;
     if (mdot_host(c, a + o, 0, 1, b + o, &r)) return NAN;
     return r;
@@ -595,7 +595,8 @@ int fgmres(iemic_ctx* c, const double* b, double* x, const iemic_krylov* opt, ie
 {
     /* vectors are ext-layout (stride NE); kernels touch the owned rows [o, o + NL) */
     const int m = std::max(1, std::min(opt->krylov_dim, MAX_KRYLOV));
-    const int64_t NE = c->sub.nerows(), o = NUN * c->sub.own0, NL = c->sub.nlrows();
+    const Owned ow = owned(c);         /* o, NL are named: the DCGS2 loop's lambda captures them */
+    const int64_t NE = c->sub.nerows(), o = ow.o, NL = ow.n;
     /* DCGS2 with the block GS: the Arnoldi basis on the active cells only.  Identity rows of J
      * (all rows of a land cell, some of an ocean cell) are identity rows of the preconditioner
      * too, so with a right-hand side that is zero on them every Krylov vector is exactly zero
@@ -629,7 +630,7 @@ int fgmres(iemic_ctx* c, const double* b, double* x, const iemic_krylov* opt, ie
     double* Z = c->kr.Z.p;
     double* w = c->kr.w.p;
     double* r = c->kr.r.p;
-    const unsigned G = grid_for(NL);
+    const unsigned G = ow.grid;
     const unsigned GC = grid_for(NC);
     Hessenberg hess(m);
     std::vector<double> h(m + 1), h2(m + 1), y(m);

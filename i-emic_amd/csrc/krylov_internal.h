@@ -1,7 +1,6 @@
 /*
- * krylov_internal.h -- what the ocean's Krylov units share (krylov.hip, idrs.hip): the launch
- * grid of their element-wise kernels, the small numeric guards, and the helpers of krylov.hip
- * that IDR(s) calls.  idrs_core.h takes the guards (sqrt0, nonfinite) from here, also for the
+ * krylov_internal.h -- what the ocean's Krylov units share (krylov.hip, idrs.hip): the small
+ * numeric guards and the helpers of krylov.hip that IDR(s) calls.  idrs_core.h takes the guards (sqrt0, nonfinite) from here, also for the
  * coupled model; included by nothing else.
  */
 #ifndef IEMIC_KRYLOV_INTERNAL_H
@@ -14,12 +13,6 @@
 #include "common.h"
 
 namespace iemic {
-
-inline unsigned grid_for(int64_t N)
-{
-    int64_t b = (N + 255) / 256;
-    return (unsigned)std::min<int64_t>(b, 2048);
-}
 
 /* sqrt of a squared norm that rounding may have driven below zero; NaN stays NaN */
 inline double sqrt0(double v) { return v > 0.0 ? std::sqrt(v) : (v == v ? 0.0 : v); }

@@ -145,7 +145,7 @@ int prec_apply(iemic_ctx* c, const double* r, double* z)
         return IEMIC_ESTATE;
     }
     if (c->gs.kind == 2) return gs_apply(c, r, z);
-    const int64_t o = NUN * c->sub.own0;
+    const int64_t o = owned(c).o;
     hipLaunchKernelGGL(k_bj_apply, dim3((unsigned)((c->sub.nloc + 255) / 256)), dim3(256), 0, c->stream,
                        c->gs.dinv.p, c->sub.nloc, r + o, z + o);
     HIP_OK(hipGetLastError());

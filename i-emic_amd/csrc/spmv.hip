@@ -419,9 +419,9 @@ static int spmv_intcond(iemic_ctx* c, const double* x, double* yr)
     hipStream_t s = c->stream;
     if (c->su.rowintcon_ref >= 0) {
         /* dense intcond row: y[rowintcon] = intSign * coeff . x (summed over the ranks) */
-        const int64_t o = NUN * c->sub.own0;
-        hipLaunchKernelGGL(k_mdot, dim3(RED_BLOCKS, 1), dim3(256), 0, s, c->d_intc.p + o, (int64_t)0, 1,
-                           x + o, c->sub.nlrows(), c->d_red.p);
+        const Owned w = owned(c);
+        hipLaunchKernelGGL(k_mdot, dim3(RED_BLOCKS, 1), dim3(256), 0, s, c->d_intc.p + w.o, (int64_t)0, 1,
+                           x + w.o, w.n, c->d_red.p);
         hipLaunchKernelGGL(k_mdot_final, dim3(1), dim3(256), 0, s, c->d_red.p, RED_BLOCKS, 1,
                            c->d_red.p + RED_BLOCKS);
         int rc = allreduce_sum(c, c->d_red.p + RED_BLOCKS, 1);

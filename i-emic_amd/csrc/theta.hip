@@ -62,20 +62,10 @@ __global__ void __launch_bounds__(256) k_theta_update(double* __restrict__ x, co
          q += (int64_t)gridDim.x * blockDim.x) {
         const double d = dx[q];
         x[q] = x[q] - d;
-        const double a = fabs(d);
-        v = (a > v || a != a) ? a : v;
+        v = nanmax(v, fabs(d));
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        const double u = __shfl_down(v, o, 64);
-        v = (u > v || u != u) ? u : v;
-    }
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = sm[0];
-        for (int w = 1; w < 4; w++) t = (sm[w] > t || sm[w] != sm[w]) ? sm[w] : t;
-        part[blockIdx.x] = t;
-    }
+    v = block_nanmax(v, sm);
+    if (threadIdx.x == 0) part[blockIdx.x] = v;
 }
 
 static int theta_ready(iemic_ctx* c, const char* who)
@@ -132,8 +122,7 @@ int theta_rhs(iemic_ctx* c)
     Theta& th = c->th;
     if ((rc = halo_exchange(c, c->d_x.p, HALO))) return rc;
     if ((rc = assemble_rhs(c, c->d_x.p, c->d_F.p))) return rc;
-    const int64_t o = NUN * c->sub.own0, NL = c->sub.nlrows();
-    const unsigned G = (unsigned)std::min<int64_t>((NL + 255) / 256, 2048);
+    const auto [o, NL, G] = owned(c);
     hipLaunchKernelGGL(k_theta_residual, dim3(G), dim3(256), 0, c->stream, th.dt * th.theta, c->d_F.p + o,
                        th.dt * (1 - th.theta), th.Fold.p + o, c->d_B.p + o, th.xold.p + o, c->d_x.p + o, th.dt,
                        th.theta, th.Ft.p + o, th.b.p + o, NL);
@@ -161,18 +150,13 @@ int theta_jacobian(iemic_ctx* c)
 /* Newton.H:95-97: x <- x - dx and this rank's ||dx||_inf */
 int theta_update(iemic_ctx* c, const double* dx, double* absmax)
 {
-    const int64_t o = NUN * c->sub.own0, NL = c->sub.nlrows();
-    const int nb = (int)std::min<int64_t>((NL + 255) / 256, RED_BLOCKS);
-    hipLaunchKernelGGL(k_theta_update, dim3(nb), dim3(256), 0, c->stream, c->d_x.p + o, dx + o, NL, c->d_part.p);
+    const Owned w = owned(c);
+    const int nb = (int)std::min<int64_t>((w.n + 255) / 256, RED_BLOCKS);
+    hipLaunchKernelGGL(k_theta_update, dim3(nb), dim3(256), 0, c->stream, c->d_x.p + w.o, dx + w.o, w.n,
+                       c->d_part.p);
     HIP_OK(hipGetLastError());
     c->jac_valid = 0;
-    std::vector<double> part(nb);
-    int rc = d2h(c, part.data(), c->d_part.p, sizeof(double) * nb);
-    if (rc) return rc;
-    double mx = 0.0;
-    for (double v : part) mx = (v > mx || v != v) ? v : mx;
-    *absmax = mx;
-    return 0;
+    return part_nanmax(c, nb, absmax);
 }
 
 /* AdaptiveTransient.H:107: the state goes back to x_n after a failed Newton run */
@@ -180,9 +164,9 @@ int theta_restore(iemic_ctx* c)
 {
     int rc = theta_ready(c, "iemic_theta_restore");
     if (rc) return rc;
-    const int64_t o = NUN * c->sub.own0;
-    HIP_OK(hipMemcpyAsync(c->d_x.p + o, c->th.xold.p + o, sizeof(double) * c->sub.nlrows(),
-                          hipMemcpyDeviceToDevice, c->stream));
+    const Owned w = owned(c);
+    HIP_OK(hipMemcpyAsync(c->d_x.p + w.o, c->th.xold.p + w.o, sizeof(double) * w.n, hipMemcpyDeviceToDevice,
+                          c->stream));
     c->jac_valid = 0;
     return 0;
 }

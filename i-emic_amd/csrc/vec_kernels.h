@@ -17,7 +17,7 @@
  * k_zero is not here: dev_zero (common.h) launches it from every unit, it does no
  * arithmetic, and its one external definition stays in krylov.hip.
  *
- * The launch grids stay with the callers (grid_for in krylov_internal.h, blocks_for in
+ * The launch grids stay with the callers (grid_for in common.h, blocks_for in
  * coupled_internal.h): the loops are grid-stride and element-wise.
  */
 #ifndef IEMIC_VEC_KERNELS_H
