@@ -132,6 +132,7 @@ int act_build(iemic_ctx* c, bool* changed)
     }
     if ((rc = act_tiles(c, h, cm))) return rc;
     as.act_h.swap(h);
+    as.gen++;
     *changed = true;
     return 0;
 }

@@ -186,6 +186,15 @@ struct TsMg {
     int crd = 0;
     int ckind = 0;                   /* how cinv was assembled: 0 device, 1 cyclic reduction, 2 host */
     bool nofuse = false;             /* test hook only: no level takes the fused launches    */
+    /* the entry kernel's operand A_TS,D (k_mg_entry_p): the T/S rows' couplings to the dynamics
+     * unknowns of the active cells, one contiguous run per tile, the identity-column slots
+     * stored as 0 (k_mg_entry_pack, once per set-up from the set-up's Jacobian); etl: per
+     * tile the run's start, its active cells and their mask (ts_mg_internal.h), rebuilt when
+     * the active set changes (egen against ActiveSet::gen) */
+    DevBuf<double> ep;
+    DevBuf<uint64_t> etl;
+    int64_t egen = -1, epn = 0;      /* epn: doubles of ep in use                             */
+    bool nopack = false;             /* test hook only: the entry reads the slot-major Jacobian */
     int hr = 0;                      /* bands: level 0 has 2 halo rows, and its colour-1   */
                                      /* lines on them are relaxed here too (mg_vcycle)      */
     SchurCR cr;
@@ -198,6 +207,9 @@ int ts_mg_setup(iemic_ctx* c, int sweeps);
  * ts_mg_out.  side: the V-cycles on iemic_ctx::side, ev_join recorded after them */
 int ts_mg_solve(iemic_ctx* c, const double* zd, double* z, bool out, bool side);
 int ts_mg_out(iemic_ctx* c, double* z);
+/* the solve's first launch alone: level 0's right-hand side from BlockGS::rrP and zd, its
+ * colour-0 lines relaxed (from the pack, or from the Jacobian when TsMg::nopack) */
+int ts_mg_entry(iemic_ctx* c, const double* zd);
 /* test_hooks.hip: the V-cycle's plan and level q as the apply leaves it (device pointers; z is
  * the iterate the level hands upward, cinv only on the coarsest level; halo: the level's
  * layout pads its rows or columns) */
@@ -227,6 +239,7 @@ struct ActiveSet {
     DevBuf<uint8_t> actf;            /* per owned cell: 1 active (k_cell_active)           */
     int64_t nact = 0;
     std::vector<uint8_t> act_h;      /* the per-cell flags the list was built from        */
+    int64_t gen = 0;                 /* counts the rebuilds of the list (act_build)       */
     /* the compressed SpMV (spmv.hip k_spmv7c): the active cells' 104 coefficients blocked
      * per tile (k_spmv_pack: no coefficient line holds a land cell or another tile's), and
      * the grid tiles that hold an active cell (8 ints each: tile, first | last active lane

@@ -4,7 +4,9 @@
  * preconditioner (coupled.hip) for tests/test_gpu_coupled_krylov.py, and the DCGS2 update pass
  * (krylov.hip) for tests/test_dcgs_fused_coef.py, and the T/S multigrid's plan, levels and
  * fusion switch (iemic_test_ts_mg_plan, iemic_test_ts_mg_level, iemic_test_ts_mg_nofuse;
- * ts_mg.hip, ts_mg_setup.hip) for tests/test_gpu_ts_mg.py, and the Ritz-vector and residual
+ * ts_mg.hip, ts_mg_setup.hip) for tests/test_gpu_ts_mg.py, its entry launch and the packed
+ * operand's switch (iemic_test_ts_mg_entry, iemic_test_ts_mg_nopack) for
+ * tests/test_gpu_ts_entry_pack.py, and the Ritz-vector and residual
  * kernels of the stability analysis (eigs.hip) for tests/test_gpu_eigs.py.  They are exported from the
  * device library but are NOT part of its public ABI (include/iemic.h, IEMIC_ABI_VERSION):
  * tests/dense_hooks.py binds them.  All pointers are host pointers; every hook runs on the
@@ -86,6 +88,18 @@ int iemic_test_ts_mg_level(iemic_ctx* ctx, int q, double* off, double* diag, dou
 
 /* on != 0: no level is visited by the fused launches (k_mg_dn / k_mg_up) until it is cleared */
 int iemic_test_ts_mg_nofuse(iemic_ctx* ctx, int on);
+
+/* on != 0: the T/S solve's entry launch reads the slot-major Jacobian (k_mg_entry) instead of
+ * the packed operand (k_mg_entry_p) until it is cleared: the pack's reference and A/B switch */
+int iemic_test_ts_mg_nopack(iemic_ctx* ctx, int on);
+
+/* The entry launch alone (ts_mg_entry) from host data: rr and zd are component-planar vectors
+ * of NE = 6 x ext cells doubles (the planar right-hand side and the dynamics iterate); level
+ * 0's right-hand side b and iterate z come back as in iemic_test_ts_mg_level (2 x ncl each;
+ * the device copies start as NaN bit patterns).  *pack_doubles (may be NULL): the doubles of
+ * the packed operand.  The preconditioner's own planar right-hand side is put back. */
+int iemic_test_ts_mg_entry(iemic_ctx* ctx, int64_t NE, const double* rr, const double* zd, double* b, double* z,
+                           int64_t* pack_doubles);
 
 /* k_eig_ritz (eigs.hip) on an arbitrary basis: V (j x ldv, ldv >= N), Y (j x p row-major),
  * X (p x N) = the p combinations sum_i Y[i][q] V_i over the first N entries of every row; the

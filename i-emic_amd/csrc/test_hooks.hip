@@ -313,6 +313,44 @@ extern "C" int iemic_test_ts_mg_nofuse(iemic_ctx* c, int on)
     return 0;
 }
 
+extern "C" int iemic_test_ts_mg_nopack(iemic_ctx* c, int on)
+{
+    if (!c) return bad("null argument");
+    c->gs.mg.nopack = on != 0;
+    return 0;
+}
+
+extern "C" int iemic_test_ts_mg_entry(iemic_ctx* c, int64_t NE, const double* rr, const double* zd, double* b,
+                                      double* z, int64_t* pack_doubles)
+{
+    if (!c || !rr || !zd || !b || !z) return bad("null argument");
+    if (c->sub.nranks != 1) return bad("a single-rank context is needed");
+    if (!c->gs.ready || c->gs.ts_mg <= 0) return bad("no T/S multigrid set up");
+    if (NE != c->sub.nerows() || (size_t)NE > c->gs.rrP.n) return bad("vector length");
+    if (hipSetDevice(c->device) != hipSuccess) return IEMIC_EDEVICE;
+    StreamGuard guard{c};
+    TsMgProbe p;
+    if (ts_mg_probe(c, 0, &p)) return bad("no T/S multigrid levels");
+    if (p.halo) return bad("the level's layout has a halo");
+    DevBuf<double> keep, zdd;
+    if (keep.alloc(NE) || zdd.alloc(NE)) return IEMIC_ENOMEM;
+    int rc;
+    /* the preconditioner's planar right-hand side is put back afterwards */
+    HIP_OK(hipMemcpyAsync(keep.p, c->gs.rrP.p, sizeof(double) * NE, hipMemcpyDeviceToDevice, c->stream));
+    if ((rc = h2d(c, c->gs.rrP.p, rr, sizeof(double) * NE))) return rc;
+    if ((rc = h2d(c, zdd.p, zd, sizeof(double) * NE))) return rc;
+    const size_t ncl = (size_t)p.n * p.m * c->l;
+    HIP_OK(hipMemsetAsync(const_cast<double*>(p.b), 0xff, sizeof(double) * 2 * ncl, c->stream));
+    HIP_OK(hipMemsetAsync(const_cast<double*>(p.z), 0xff, sizeof(double) * 2 * ncl, c->stream));
+    if ((rc = ts_mg_entry(c, zdd.p))) return rc;
+    HIP_OK(hipGetLastError());
+    if ((rc = d2h(c, b, p.b, sizeof(double) * 2 * ncl))) return rc;
+    if ((rc = d2h(c, z, p.z, sizeof(double) * 2 * ncl))) return rc;
+    HIP_OK(hipMemcpyAsync(c->gs.rrP.p, keep.p, sizeof(double) * NE, hipMemcpyDeviceToDevice, c->stream));
+    if (pack_doubles) *pack_doubles = c->gs.mg.epn;
+    return dev_wait(c, nullptr, __func__);
+}
+
 extern "C" int iemic_test_eig_ritz(iemic_ctx* c, int j, int p, int64_t N, int64_t ldv, const double* V,
                                    const double* Y, double* X)
 {

@@ -582,8 +582,8 @@ __global__ void __launch_bounds__(10 * P) k_mg_up(TsLev F, TsLev C, double* __re
  * latitude row (Jacobian slots read along i, coalesced; identity-row columns skipped by
  * the slot bitmask), transposed through LDS into the k-contiguous level layout, then the
  * tile's colour-0 lines relaxed from the zero iterate and the other columns' iterate set
- * to 0 (one launch instead of rhs + first colour). */
-constexpr int MG_TI = 16;
+ * to 0 (one launch instead of rhs + first colour).  This is the route from the slot-major
+ * Jacobian: the reference of k_mg_entry_p below (TsMg::nopack). */
 template <int P>
 __global__ void __launch_bounds__(256) k_mg_entry(const double* __restrict__ val, const uint8_t* __restrict__ knP,
                                                  const uint64_t* __restrict__ kmask,
@@ -630,6 +630,94 @@ __global__ void __launch_bounds__(256) k_mg_entry(const double* __restrict__ val
         if (mg_lcolour(V, i, jl) == 0) {
             double xt, xs;
             line_solve<P>(V.fac + c, V.cstr, on, k, bt, bs, xt, xs);
+            if (on) {
+                V.z[c] = xt;
+                V.z[V.cstr + c] = xs;
+            }
+        } else if (on) {
+            V.z[c] = 0.0;
+            V.z[V.cstr + c] = 0.0;
+        }
+    }
+}
+
+/* The same launch on the packed operand (TsMg::ep, ts_mg_internal.h): the same tile, a thread
+ * per cell of it forms both rows -- they read the same ten entries of z_D -- from the tile's
+ * own contiguous run: a wave's load of one term is one run of its active lanes' doubles, no
+ * line holds a land cell or another tile's, and no load waits for a slot mask (the masked
+ * slots are stored as the 0.0 bts_row takes for them).  A lane finds its place in the run
+ * from the tile's active-cell mask (popcount).  The loads of a cell are written before its
+ * first sum.  (Loading the first colour-0 column's line factors ahead of all that holds 24
+ * more registers through the sums, 98 VGPRs against 64, gains nothing and makes the
+ * compiler contract the line solve differently: DESIGN.md §4.)  The sums are
+ * bts_row's, term by term in its order, identity rows 0, and the line solve is the same
+ * line_solve: level 0's b and z come out bitwise as from k_mg_entry. */
+template <int P>
+__global__ void __launch_bounds__(256) k_mg_entry_p(const double* __restrict__ ep, const uint64_t* __restrict__ etl,
+                                                   int nw, const uint8_t* __restrict__ knP,
+                                                   const double* __restrict__ rr, const double* __restrict__ z,
+                                                   Lay L, TsLev V)
+{
+    LAY_ALIASES;
+    __shared__ double sb[2][64][MG_TI + 1];
+    const int nx = L.nx;
+    const int tiles = (nx + MG_TI - 1) / MG_TI;
+    const int jl = blockIdx.x / tiles, i0 = (blockIdx.x % tiles) * MG_TI;
+    const int j = L.jb0 + jl;
+    const SubLay X = sub_of(L);
+    const uint64_t* e = etl + (int64_t)blockIdx.x * (2 + nw);
+    const int64_t na = (int64_t)e[1];
+    const double* run = ep + (int64_t)e[0];
+    const int grp = threadIdx.x / P, kl = threadIdx.x % P, ng = blockDim.x / P;
+    const bool on = kl < l;
+    for (int q = threadIdx.x; q < l * MG_TI; q += blockDim.x) {
+        const int k = q / MG_TI, ii = q % MG_TI;
+        double at = 0.0, as = 0.0;
+        if ((e[2 + (q >> 6)] >> (q & 63)) & 1) {
+            const double* p = run + mg_entry_rank(e, q);
+            double vt[MG_NE], vs[MG_NE], zz[MG_NE];
+#pragma unroll
+            for (int d = 0; d < MG_NE; d++) {
+                vt[d] = p[d * na];
+                vs[d] = p[(MG_NE + d) * na];
+            }
+            const int i = i0 + ii;
+            const int64_t cell = L.own0 + ((int64_t)jl * l + k) * nx + i;
+            int nc[3][9];
+            nb_cells(X, i, j, k, nc);
+#pragma unroll
+            for (int d = 0; d < MG_NE; d++) {
+                const Slot sl = SLOTS[MG_ES.s[0][d]];
+                zz[d] = z[(int64_t)nc[sl.di + 1][(sl.dk + 1) * 3 + (sl.dj + 1)] + L.ps * sl.var];
+            }
+            const int64_t rt = PL(cell, TT), rs = PL(cell, SS);
+            const uint8_t idt = knP[rt], ids = knP[rs];
+            at = rr[rt];
+            as = rr[rs];
+#pragma unroll
+            for (int d = 0; d < MG_NE; d++) {
+                at -= vt[d] * zz[d];
+                as -= vs[d] * zz[d];
+            }
+            if (idt) at = 0.0;
+            if (ids) as = 0.0;
+        }
+        sb[0][k][ii] = at;
+        sb[1][k][ii] = as;
+    }
+    __syncthreads();
+    for (int ii = grp; ii < MG_TI; ii += ng) {
+        const int i = i0 + ii;
+        if (i >= nx) break;
+        const int64_t c = on ? mg_cell(V, i, jl, kl) : 0;
+        const double bt = on ? sb[0][kl][ii] : 0.0, bs = on ? sb[1][kl][ii] : 0.0;
+        if (on) {
+            V.b[c] = bt;
+            V.b[V.cstr + c] = bs;
+        }
+        if (mg_lcolour(V, i, jl) == 0) {
+            double xt, xs;
+            line_solve<P>(V.fac + c, V.cstr, on, kl, bt, bs, xt, xs);
             if (on) {
                 V.z[c] = xt;
                 V.z[V.cstr + c] = xs;
@@ -890,7 +978,9 @@ static int mg_vcycle(iemic_ctx* c, int q, bool first, double* zout)
  * write only the multigrid's own buffers once the entry kernel has formed the right-hand
  * side) run on the side stream, forked after the entry kernel; gs_apply joins before
  * ts_mg_out. */
-int ts_mg_solve(iemic_ctx* c, const double* zd, double* z, bool out, bool side)
+/* the entry launch: from the packed operand of the last set-up (every decomposition: it
+ * forms the owned rows only), or from the Jacobian when the test hook asks (TsMg::nopack) */
+int ts_mg_entry(iemic_ctx* c, const double* zd)
 {
     BlockGS& gs = c->gs;
     const Lay L = lay_of(c->sub);
@@ -898,16 +988,27 @@ int ts_mg_solve(iemic_ctx* c, const double* zd, double* z, bool out, bool side)
     const TsLev V0 = mg_view(c, 0);
     const unsigned ge = (unsigned)(((c->sub.nx + MG_TI - 1) / MG_TI) * V0.mb);
     with_lanes(mg_lanes(c->l), [&](auto p) {
-        hipLaunchKernelGGL(k_mg_entry<LANES_OF(p)>, dim3(ge), dim3(256), 0, s, gs.act.vp, gs.knP.p, gs.kmask.p,
-                           gs.rrP.p, zd, L, V0);
+        if (gs.mg.nopack)
+            hipLaunchKernelGGL(k_mg_entry<LANES_OF(p)>, dim3(ge), dim3(256), 0, s, gs.act.vp, gs.knP.p,
+                               gs.kmask.p, gs.rrP.p, zd, L, V0);
+        else
+            hipLaunchKernelGGL(k_mg_entry_p<LANES_OF(p)>, dim3(ge), dim3(256), 0, s, (const double*)gs.mg.ep.p,
+                               (const uint64_t*)gs.mg.etl.p, mg_entry_words(c->l), gs.knP.p, gs.rrP.p, zd, L, V0);
     });
+    return 0;
+}
+
+int ts_mg_solve(iemic_ctx* c, const double* zd, double* z, bool out, bool side)
+{
+    BlockGS& gs = c->gs;
+    int rc;
+    if ((rc = ts_mg_entry(c, zd))) return rc;
     auto cycles = [&]() {
         int rc = 0;
         for (int cyc = 0; cyc < gs.ts_mg && !rc; cyc++)
             rc = mg_vcycle(c, 0, cyc == 0, out && cyc + 1 == gs.ts_mg ? z : nullptr);
         return rc;
     };
-    int rc;
     if (side) {
         OnSide on(c);
         HIP_OK(on.err);

@@ -29,6 +29,49 @@ __host__ __device__ __forceinline__ int64_t mg_cell(const TsLev& V, int i, int j
     return (((int64_t)jl + V.hj) * (V.n + 2 * V.hi) + i + V.hi) * V.l + k;
 }
 
+/* The entry kernel's tile (k_mg_entry, k_mg_entry_p): MG_TI columns of one latitude row over
+ * the full depth, cell q = k MG_TI + ii of the tile.  Its packed operand A_TS,D (TsMg::ep,
+ * k_mg_entry_pack): the T and S rows' slots whose columns are dynamics unknowns, listed here
+ * once from the slot table in the rows' own order (the order bts_row accumulates in). */
+constexpr int MG_TI = 16;
+struct EntrySlots {
+    int n[2];                        /* dynamics slots of the T row, of the S row            */
+    int s[2][20];                    /* their indices in SLOTS                               */
+};
+constexpr EntrySlots entry_slots()
+{
+    EntrySlots E{};
+    for (int R = 0; R < 2; R++)
+        for (int s = ROW_BEGIN[TT + R]; s < ROW_BEGIN[TT + R + 1]; s++)
+            if (SLOTS[s].var != TT && SLOTS[s].var != SS) E.s[R][E.n[R]++] = s;
+    return E;
+}
+constexpr EntrySlots MG_ES = entry_slots();
+constexpr int MG_NE = MG_ES.n[0];    /* terms per row (10)                                   */
+/* the two rows read the same columns in the same order, so one gather of z serves both */
+constexpr bool entry_slots_match()
+{
+    if (MG_ES.n[0] != MG_ES.n[1]) return false;
+    for (int d = 0; d < MG_ES.n[0]; d++) {
+        const Slot a = SLOTS[MG_ES.s[0][d]], b = SLOTS[MG_ES.s[1][d]];
+        if (a.di != b.di || a.dj != b.dj || a.dk != b.dk || a.var != b.var) return false;
+    }
+    return true;
+}
+static_assert(entry_slots_match(), "the T and S rows' dynamics slots differ");
+/* a tile's descriptor in TsMg::etl, 2 + nw 64-bit words: the first double of its run in ep,
+ * its active cells na, the active-cell mask (bit q & 63 of word q >> 6).  The run holds term
+ * d of row R (0 T, 1 S) of the r-th active cell at (R MG_NE + d) na + r, and starts on a
+ * 128-byte line that no other tile shares. */
+__host__ __device__ __forceinline__ int mg_entry_words(int l) { return (MG_TI * l + 63) / 64; }
+__device__ __forceinline__ int mg_entry_rank(const uint64_t* __restrict__ e, int q)
+{
+    const int w = q >> 6, bit = q & 63;
+    int r = __popcll(e[2 + w] & (((uint64_t)1 << bit) - 1));
+    for (int u = 0; u < w; u++) r += __popcll(e[2 + u]);
+    return r;
+}
+
 /* decode of a halo-free level's cell index t = (jl n + i) l + k */
 __host__ __device__ __forceinline__ void mg_decode(int64_t t, int n, int l, int& i, int& jl, int& k)
 {

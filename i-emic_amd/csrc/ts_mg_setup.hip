@@ -46,6 +46,34 @@ __global__ void k_mg_pack0(const double* __restrict__ tsoff, const double* __res
     for (int e = 0; e < 4; e++) diag[(int64_t)e * V.cstr + c] = tsdiag[(int64_t)e * next + cell];
 }
 
+/* the entry kernel's operand (ts_mg_internal.h): one thread per (tile, cell of the tile); an
+ * active cell writes its 2 MG_NE terms, a slot that couples to an identity column (kmask) as
+ * the 0.0 bts_row puts in its place */
+__global__ void k_mg_entry_pack(const double* __restrict__ val, const uint64_t* __restrict__ kmask,
+                                const uint64_t* __restrict__ etl, int nw, Lay L, int64_t nt,
+                                double* __restrict__ ep)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= nt) return;
+    const int tc = MG_TI * L.l, tiles = (L.nx + MG_TI - 1) / MG_TI;
+    const int q = (int)(t % tc);
+    const int64_t tile = t / tc;
+    const uint64_t* e = etl + tile * (2 + nw);
+    if (!((e[2 + (q >> 6)] >> (q & 63)) & 1)) return;
+    const int64_t na = (int64_t)e[1];
+    double* p = ep + (int64_t)e[0] + mg_entry_rank(e, q);
+    const int jl = (int)(tile / tiles), i = (int)(tile % tiles) * MG_TI + q % MG_TI, k = q / MG_TI;
+    const int64_t lc = ((int64_t)jl * L.l + k) * L.nx + i;
+    const uint64_t kb = kmask[2 * (L.own0 + lc) + 1];
+#pragma unroll
+    for (int R = 0; R < 2; R++)
+#pragma unroll
+        for (int d = 0; d < MG_NE; d++) {
+            const int s = MG_ES.s[R][d];
+            p[(R * MG_NE + d) * na] = ((kb >> (s - 64)) & 1) ? 0.0 : val[(int64_t)s * L.nloc + lc];
+        }
+}
+
 /* Galerkin coarse operator: sum of the children's blocks and couplings; couplings inside
  * the aggregate go to the coarse 2x2 block */
 __global__ void k_mg_galerkin(TsLev F, TsLev C, double* __restrict__ off, double* __restrict__ diag)
@@ -609,6 +637,48 @@ static int mg_coarse_host(iemic_ctx* c, int qc, int64_t ncl, int N)
     return mg_global_setup(c, off, dg);
 }
 
+/* The entry kernel's packed operand from the set-up's Jacobian (ActiveSet::vp) and the slot
+ * masks: reads nothing else, so under gs_factor's overlap it runs on the side stream with the
+ * rest of this set-up.  The tiles' descriptors follow the active set (host, from its flags)
+ * and are rebuilt only when that changes.  Owned rows only, whatever the decomposition: the
+ * entry kernel forms no other row (a band's halo rows arrive by mg_halo2). */
+static int mg_entry_pack(iemic_ctx* c)
+{
+    TsMg& mg = c->gs.mg;
+    const ActiveSet& as = c->gs.act;
+    const int nx = c->sub.nx, mb = c->sub.mb, l = c->l;
+    const int tiles = (nx + MG_TI - 1) / MG_TI, nw = mg_entry_words(l), S = 2 + nw;
+    int rc;
+    if (mg.egen != as.gen || !mg.etl.p) {
+        std::vector<uint64_t> d((size_t)tiles * mb * S, 0);
+        int64_t base = 0;
+        for (int jl = 0; jl < mb; jl++)
+            for (int ti = 0; ti < tiles; ti++) {
+                uint64_t* e = &d[((size_t)jl * tiles + ti) * S];
+                int64_t na = 0;
+                for (int k = 0; k < l; k++)
+                    for (int ii = 0; ii < MG_TI && ti * MG_TI + ii < nx; ii++)
+                        if (as.act_h[((size_t)jl * l + k) * nx + ti * MG_TI + ii]) {
+                            const int q = k * MG_TI + ii;
+                            e[2 + (q >> 6)] |= (uint64_t)1 << (q & 63);
+                            na++;
+                        }
+                e[0] = (uint64_t)base;
+                e[1] = (uint64_t)na;
+                base += (2 * MG_NE * na + 15) / 16 * 16;
+            }
+        if (mg.etl.reserve(d.size() + 1) || mg.ep.reserve((size_t)base + 16)) return IEMIC_ENOMEM;
+        if ((rc = h2d(c, mg.etl.p, d.data(), sizeof(uint64_t) * d.size()))) return rc;
+        mg.epn = base;
+        mg.egen = as.gen;
+    }
+    const int64_t nt = (int64_t)tiles * mb * MG_TI * l;
+    hipLaunchKernelGGL(k_mg_entry_pack, dim3(blocks_for(nt)), dim3(256), 0, c->stream, c->gs.act.vp,
+                       (const uint64_t*)c->gs.kmask.p, (const uint64_t*)mg.etl.p, nw, lay_of(c->sub), nt, mg.ep.p);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
 /* levels, Galerkin operators, z-line factors and the coarsest inverse (once per Jacobian) */
 int ts_mg_setup(iemic_ctx* c, int sweeps)
 {
@@ -628,6 +698,7 @@ int ts_mg_setup(iemic_ctx* c, int sweeps)
         if ((rc = mg_levels(c))) return rc;
         if (gs.ts_mg == 0) return 0;
     }
+    if ((rc = mg_entry_pack(c))) return rc;
     if ((rc = mg_operators(c))) return rc;
     const int qc = gs.mg.nlev - 1;
     const int64_t ncl = (int64_t)gs.mg.n[qc] * gs.mg.m[qc] * c->l;
