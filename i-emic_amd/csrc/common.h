@@ -674,6 +674,11 @@ int eigs_end(iemic_ctx* c);
  * Y: host, j x p row-major; V and xs point at the first row the launch covers */
 int eigs_ritz(iemic_ctx* c, const double* V, int64_t ldv, int j, int p, const double* Y, double* const* xs,
               int64_t N);
+/* V[:, q] <- sum_i Q[i p + q] V[:, i] (i < j, q < p) and V[:, p] <- V[:, j] over N rows, in place,
+ * one pass (stride ldv); Q: host, j x p row-major; 1 <= p < j, p <= 16; V points at the first row */
+int eigs_compress(iemic_ctx* c, double* V, int64_t ldv, int j, int p, const double* Q, int64_t N);
+/* thick restart of the run in progress on Q (j x p): the basis compressed, t = B v_p, j <- p */
+int eigs_restart(iemic_ctx* c, int p, const double* Q);
 /* out2 = sum |a - mu B x|^2, sum |a|^2 over N rows (a, x complex; ai = xi = null: real),
  * summed over the ranks; pointers at the first row */
 int eigs_residual_sums(iemic_ctx* c, const double* ar, const double* ai, const double* xr, const double* xi,

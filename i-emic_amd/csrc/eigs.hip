@@ -15,6 +15,8 @@
  *                 the inner product that leaves the P rows out (k_eig_drop_p),
  *                 h_{j+1,j} = ||w||, v_{j+1} = w / h_{j+1,j} and t = B v_{j+1} in one kernel
  *   eigs_ritz     all p Ritz vectors in one pass over the basis (k_eig_ritz)
+ *   eigs_restart  thick (Krylov-Schur) restart: the basis compressed onto p kept directions in
+ *                 place, in one pass (k_eig_compress), the residual vector moved behind them
  *   eigs_residual ||(J - sigma B) x - (lambda - sigma) B x|| and ||(J - sigma B) x|| in one pass
  *                 over two SpMV outputs (k_eig_residual), the products and the difference in
  *                 double-double (k_spmv_dd, k_eig_intcond_dd)
@@ -153,6 +155,69 @@ __global__ void __launch_bounds__(256) k_eig_ritz(const double* __restrict__ V, 
                 if (in0) out.x[q][q0] = a0[q];
                 if (in1) out.x[q][q1] = a1[q];
             }
+    }
+}
+
+/* The thick restart's pass over the basis, in place: V_q <- sum_{i<j} Q[i][q] V_i for q < p and
+ * V_p <- V_j, columns p + 1 .. j untouched.  Row r of the result depends on row r of the basis
+ * alone, and a row belongs to one lane of one block: the lane reads its j + 1 values of the
+ * row (the sums, then V_j) before it stores any of the p + 1, so the overlap of outputs and
+ * inputs is harmless.  V is therefore not __restrict__, and the stores stay behind the loads.
+ * Otherwise k_eig_ritz's shape: tiles of 512 rows, a lane two rows 256 apart, Q (j x P
+ * row-major, padded with zero columns) in LDS, 2 P accumulators in registers, contiguous
+ * 512-byte wave loads and stores.  Only rows < N are touched.  Needs p < j (so column p is
+ * one of the j + 1).  Algorithmic bytes (j + 1 + p + 1) N 8. */
+template <int P>
+__global__ void __launch_bounds__(256) k_eig_compress(double* V, int64_t ldv, int j, const double* __restrict__ Q,
+                                                      int p, int64_t N)
+{
+    __shared__ double qs[IEMIC_EIGS_MAX_M * P];
+    for (int i = threadIdx.x; i < j * P; i += blockDim.x) qs[i] = Q[i];
+    __syncthreads();
+    for (int64_t base = (int64_t)blockIdx.x * 512; base < N; base += (int64_t)gridDim.x * 512) {
+        const int64_t q0 = base + threadIdx.x, q1 = q0 + 256;
+        const bool in0 = q0 < N, in1 = q1 < N;
+        double a0[P], a1[P];
+#pragma unroll
+        for (int q = 0; q < P; q++) a0[q] = a1[q] = 0.0;
+        int i = 0;
+        for (; i + 4 <= j; i += 4) {
+            const double* v = V + (int64_t)i * ldv;
+            double x0[4], x1[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                x0[u] = in0 ? v[u * ldv + q0] : 0.0;
+                x1[u] = in1 ? v[u * ldv + q1] : 0.0;
+            }
+#pragma unroll
+            for (int u = 0; u < 4; u++)
+#pragma unroll
+                for (int q = 0; q < P; q++) {
+                    const double y = qs[(i + u) * P + q];
+                    a0[q] += y * x0[u];
+                    a1[q] += y * x1[u];
+                }
+        }
+        for (; i < j; i++) {
+            const double x0 = in0 ? V[(int64_t)i * ldv + q0] : 0.0;
+            const double x1 = in1 ? V[(int64_t)i * ldv + q1] : 0.0;
+#pragma unroll
+            for (int q = 0; q < P; q++) {
+                const double y = qs[i * P + q];
+                a0[q] += y * x0;
+                a1[q] += y * x1;
+            }
+        }
+        const double l0 = in0 ? V[(int64_t)j * ldv + q0] : 0.0;
+        const double l1 = in1 ? V[(int64_t)j * ldv + q1] : 0.0;
+#pragma unroll
+        for (int q = 0; q < P; q++)
+            if (q < p) {
+                if (in0) V[(int64_t)q * ldv + q0] = a0[q];
+                if (in1) V[(int64_t)q * ldv + q1] = a1[q];
+            }
+        if (in0) V[(int64_t)p * ldv + q0] = l0;
+        if (in1) V[(int64_t)p * ldv + q1] = l1;
     }
 }
 
@@ -518,6 +583,89 @@ int eigs_ritz(iemic_ctx* c, const double* V, int64_t ldv, int j, int p, const do
     }
     HIP_OK(hipGetLastError());
     DEV_SYNC(c);   /* the staging area is free again on return */
+    return 0;
+}
+
+template <int P>
+static void compress_launch(iemic_ctx* c, double* V, int64_t ldv, int j, const double* Qd, int p, int64_t N)
+{
+    const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>((N + 511) / 512, 2048));
+    hipLaunchKernelGGL(k_eig_compress<P>, dim3(g), dim3(256), 0, c->stream, V, ldv, j, Qd, p, N);
+}
+
+int eigs_compress(iemic_ctx* c, double* V, int64_t ldv, int j, int p, const double* Q, int64_t N)
+{
+    if (j < 2 || j > IEMIC_EIGS_MAX_M || p < 1 || p > RITZ_MAX_P || p >= j || !V || !Q || N < 0 || ldv < N) {
+        set_error("eigs_compress: needs 1 <= p < j <= IEMIC_EIGS_MAX_M, p <= 16 and ldv >= N");
+        return IEMIC_EINVAL;
+    }
+    const int P = p <= 1 ? 1 : p <= 2 ? 2 : p <= 4 ? 4 : p <= 8 ? 8 : 16;
+    /* Q padded to P columns, through the pinned staging area */
+    std::vector<double> qp((size_t)j * P, 0.0);
+    for (int i = 0; i < j; i++)
+        for (int q = 0; q < p; q++) qp[(size_t)i * P + q] = Q[(size_t)i * p + q];
+    int rc = upload_coeffs(c, qp.data(), j * P);
+    if (rc) return rc;
+    const double* Qd = c->d_hbuf.p + RED_ROWS;
+    switch (P) {
+    case 1: compress_launch<1>(c, V, ldv, j, Qd, p, N); break;
+    case 2: compress_launch<2>(c, V, ldv, j, Qd, p, N); break;
+    case 4: compress_launch<4>(c, V, ldv, j, Qd, p, N); break;
+    case 8: compress_launch<8>(c, V, ldv, j, Qd, p, N); break;
+    default: compress_launch<16>(c, V, ldv, j, Qd, p, N); break;
+    }
+    HIP_OK(hipGetLastError());
+    DEV_SYNC(c);   /* the staging area is free again on return */
+    return 0;
+}
+
+/* Thick restart: A V_j = V_j G + v_{j+1} g^T becomes A V' = V' S + v_{j+1} b^T with V' = V_j Q,
+ * S = Q^T G Q and b = Q^T g, for Q whose span is invariant under G (the caller's algebra).  The
+ * next right-hand side is rebuilt from the moved vector: iemic_eigs_ritz and
+ * iemic_eigs_residual may have used the work vectors since the last step. */
+int eigs_restart(iemic_ctx* c, int p, const double* Q)
+{
+    Eigs& eg = c->eg;
+    if (!eg.active) {
+        set_error("iemic_eigs_restart: no run in progress (iemic_eigs_begin)");
+        return IEMIC_ESTATE;
+    }
+    if (eg.broke) {
+        set_error("iemic_eigs_restart: the run ended at a breakdown (invariant Krylov space)");
+        return IEMIC_ESTATE;
+    }
+    const int j = eg.j;
+    if (p < 1) {
+        set_error("iemic_eigs_restart: p must be at least 1");
+        return IEMIC_EINVAL;
+    }
+    if (p > RITZ_MAX_P) {
+        set_error("iemic_eigs_restart: p exceeds 16 (one compression pass)");
+        return IEMIC_EINVAL;
+    }
+    if (p >= j) {
+        set_error("iemic_eigs_restart: p must be smaller than the number of steps taken, j = " + std::to_string(j));
+        return IEMIC_EINVAL;
+    }
+    if (!Q) {
+        set_error("iemic_eigs_restart: Q is null");
+        return IEMIC_EINVAL;
+    }
+    for (int i = 0; i < j * p; i++)
+        if (!std::isfinite(Q[i])) {
+            set_error("iemic_eigs_restart: non-finite entry in Q");
+            return IEMIC_EINVAL;
+        }
+    const int64_t NE = c->sub.nerows();
+    const auto [o, NL, G] = owned(c);
+    int rc = eigs_compress(c, eg.V.p + o, NE, j, p, Q, NL);
+    if (rc) return rc;
+    /* t = B v_p; w takes the copy k_eig_scale_bmul writes (the next solve overwrites it) */
+    hipLaunchKernelGGL(k_eig_scale_bmul, dim3(G), dim3(256), 0, c->stream, eg.V.p + (int64_t)p * NE + o,
+                       c->d_B.p + o, 1.0, eg.w.p + o, eg.t.p + o, NL);
+    HIP_OK(hipGetLastError());
+    DEV_SYNC(c);
+    eg.j = p;
     return 0;
 }
 

@@ -321,6 +321,13 @@ extern "C" int iemic_eigs_ritz(iemic_ctx* c, int j, int p, const double* Y, void
     return eigs_ritz(c, c->eg.V.p + w.o, c->sub.nerows(), j, p, Y, xs, w.n);
 }
 
+/* JDQZ's restart from jmax back to jmin search directions, here on an Arnoldi decomposition */
+extern "C" int iemic_eigs_restart(iemic_ctx* c, int p, const double* Q)
+{
+    CTX_CHECK(c);
+    return eigs_restart(c, p, Q);
+}
+
 /* the residual JDQZ reports per converged pair, measured on the operator itself */
 extern "C" int iemic_eigs_residual(iemic_ctx* c, double lam_re, double lam_im, double* x_re, double* x_im,
                                    double out[2])

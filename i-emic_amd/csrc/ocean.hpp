@@ -261,6 +261,9 @@ class Ocean {
     {
         check(iemic_eigs_ritz(ctx_, j, p, Y, xvecs), "eigsRitz");
     }
+    /* thick restart on Q (j x p row-major, orthonormal, invariant under the caller's Rayleigh
+     * matrix): the basis becomes [V_j Q, v_{j+1}], j <- p, and eigsStep goes on from there */
+    void eigsRestart(int p, const double* Q) { check(iemic_eigs_restart(ctx_, p, Q), "eigsRestart"); }
     /* out = ||(J - sigma B) x - (lambda - sigma) B x||, ||(J - sigma B) x|| */
     void eigsResidual(double lamRe, double lamIm, double* xRe, double* xIm, double out[2])
     {

@@ -107,6 +107,18 @@ int iemic_test_ts_mg_entry(iemic_ctx* ctx, int64_t NE, const double* rr, const d
 int iemic_test_eig_ritz(iemic_ctx* ctx, int j, int p, int64_t N, int64_t ldv, const double* V, const double* Y,
                         double* X);
 
+/* k_eig_compress (eigs.hip) on an arbitrary basis, in place: V ((j + 1) x ldv, ldv >= N, in-out),
+ * Q (j x p row-major), 1 <= p < j <= IEMIC_EIGS_MAX_M, p <= 16.  On return columns 0 .. p - 1 hold
+ * sum_i Q[i][q] V_i and column p the old column j over the first N entries of every row; the
+ * whole device copy comes back, so the caller sees what else was written. */
+int iemic_test_eig_compress(iemic_ctx* ctx, int j, int p, int64_t N, int64_t ldv, double* V, const double* Q);
+
+/* Measurement helper: on a basis of j + 1 vectors of the context's own layout, GPU milliseconds
+ * (events) of nrep thick-restart compressions by k_eig_compress (ms[0 .. nrep)) and of what
+ * it replaces (ms[nrep .. 2 nrep)): k_eig_ritz into p scratch vectors, p copies back and the
+ * copy of column j to column p.  Both sides include their upload of the j x p coefficients. */
+int iemic_test_eig_compress_cost(iemic_ctx* ctx, int j, int p, int nrep, double* ms);
+
 /* k_eig_residual and its second stage (eigs.hip) on host data of length N: out2 = sum |a - mu B
  * x|^2, sum |a|^2 with a = ar + i ai, x = xr + i xi, mu = mu_r + i mu_i; ai = xi = NULL: real. */
 int iemic_test_eig_residual(iemic_ctx* ctx, int64_t N, const double* ar, const double* ai, const double* xr,

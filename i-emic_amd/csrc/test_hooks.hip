@@ -369,6 +369,64 @@ extern "C" int iemic_test_eig_ritz(iemic_ctx* c, int j, int p, int64_t N, int64_
     return d2h(c, X, xd.p, sizeof(double) * p * N);
 }
 
+extern "C" int iemic_test_eig_compress(iemic_ctx* c, int j, int p, int64_t N, int64_t ldv, double* V, const double* Q)
+{
+    if (!c || !V || !Q) return bad("null argument");
+    if (j < 2 || j > IEMIC_EIGS_MAX_M || p < 1 || p > 16 || p >= j || N < 1 || N > (1 << 24) || ldv < N)
+        return bad("compression shape out of range");
+    if (hipSetDevice(c->device) != hipSuccess) return IEMIC_EDEVICE;
+    DevBuf<double> vd;
+    if (vd.alloc((size_t)(j + 1) * ldv)) return IEMIC_ENOMEM;
+    int rc;
+    if ((rc = h2d(c, vd.p, V, sizeof(double) * (j + 1) * ldv))) return rc;
+    if ((rc = eigs_compress(c, vd.p, ldv, j, p, Q, N))) return rc;
+    return d2h(c, V, vd.p, sizeof(double) * (j + 1) * ldv);
+}
+
+extern "C" int iemic_test_eig_compress_cost(iemic_ctx* c, int j, int p, int nrep, double* ms)
+{
+    if (!c || !ms) return bad("null argument");
+    if (j < 2 || j > IEMIC_EIGS_MAX_M || p < 1 || p > 16 || p >= j || nrep < 1 || nrep > 100)
+        return bad("compression shape out of range");
+    if (hipSetDevice(c->device) != hipSuccess) return IEMIC_EDEVICE;
+    StreamGuard guard{c};
+    const int64_t NE = c->sub.nerows();
+    const Owned w = owned(c);
+    DevBuf<double> vd, xd;
+    if (vd.alloc((size_t)(j + 1) * NE) || xd.alloc((size_t)p * NE)) return IEMIC_ENOMEM;
+    int rc;
+    /* every entry 0x3f3f3f3f3f3f3f3f = 4.8e-4 and Q the leading columns of the identity: the
+     * basis stays what it is however often the pass is repeated */
+    HIP_OK(hipMemsetAsync(vd.p, 0x3f, sizeof(double) * (j + 1) * NE, c->stream));
+    if ((rc = dev_zero(c, xd.p, (int64_t)p * NE))) return rc;
+    std::vector<double> Q((size_t)j * p, 0.0);
+    for (int q = 0; q < p; q++) Q[(size_t)q * p + q] = 1.0;
+    double* xs[16] = {};
+    for (int q = 0; q < p; q++) xs[q] = xd.p + (int64_t)q * NE + w.o;
+    EventPair ev;
+    if (ev.create()) return IEMIC_EDEVICE;
+    for (int r = 0; r < 2 * nrep; r++) {
+        const bool alt = r >= nrep;
+        HIP_OK(hipEventRecord(ev.a, c->stream));
+        if (!alt) {
+            if ((rc = eigs_compress(c, vd.p + w.o, NE, j, p, Q.data(), w.n))) return rc;
+        } else {
+            if ((rc = eigs_ritz(c, vd.p + w.o, NE, j, p, Q.data(), xs, w.n))) return rc;
+            for (int q = 0; q < p; q++)
+                HIP_OK(hipMemcpyAsync(vd.p + (int64_t)q * NE + w.o, xs[q], sizeof(double) * w.n,
+                                      hipMemcpyDeviceToDevice, c->stream));
+            HIP_OK(hipMemcpyAsync(vd.p + (int64_t)p * NE + w.o, vd.p + (int64_t)j * NE + w.o, sizeof(double) * w.n,
+                                  hipMemcpyDeviceToDevice, c->stream));
+        }
+        HIP_OK(hipEventRecord(ev.b, c->stream));
+        HIP_OK(hipEventSynchronize(ev.b));
+        float t = 0.f;
+        HIP_OK(hipEventElapsedTime(&t, ev.a, ev.b));
+        ms[r] = t;
+    }
+    return 0;
+}
+
 extern "C" int iemic_test_eig_residual(iemic_ctx* c, int64_t N, const double* ar, const double* ai, const double* xr,
                                        const double* xi, const double* B, double mu_r, double mu_i, double* out2)
 {

@@ -184,6 +184,7 @@ def lib():
         "iemic_eigs_begin": (C.c_int, [vp, C.c_double, C.c_int, C.c_uint64, P(Krylov)]),
         "iemic_eigs_step": (C.c_int, [vp, P(Krylov), PD, P(EigsInfo)]),
         "iemic_eigs_ritz": (C.c_int, [vp, C.c_int, C.c_int, PD, P(vp)]),
+        "iemic_eigs_restart": (C.c_int, [vp, C.c_int, PD]),
         "iemic_eigs_residual": (C.c_int, [vp, C.c_double, C.c_double, vp, vp, PD]),
         "iemic_eigs_end": (C.c_int, [vp]),
         "iemic_vec_alloc": (C.c_int, [vp, P(vp)]),
@@ -267,7 +268,7 @@ EXPORTED = ("iemic_abi_version", "iemic_create", "iemic_create_dist", "iemic_com
             "iemic_solve_dev", "iemic_newton_step", "iemic_theta_init_step", "iemic_theta_rhs",
             "iemic_theta_jacobian", "iemic_theta_restore", "iemic_theta_newton_step",
             "iemic_shifted_jacobian", "iemic_eigs_begin", "iemic_eigs_step", "iemic_eigs_ritz",
-            "iemic_eigs_residual", "iemic_eigs_end", "iemic_vec_alloc", "iemic_vec_free",
+            "iemic_eigs_restart", "iemic_eigs_residual", "iemic_eigs_end", "iemic_vec_alloc", "iemic_vec_free",
             "iemic_vec_update", "iemic_vec_dot", "iemic_vec_norm_inf", "iemic_vec_from_ref",
             "iemic_vec_to_ref", "iemic_state_vec", "iemic_rhs_vec", "iemic_time_spmv", "iemic_time_spmv_cold", "iemic_time_prec",
             "iemic_time_prec_parts",

@@ -698,10 +698,21 @@ class Ocean:
         computeJacobian restores J.  A non-finite sigma raises IemicError by name."""
         check(lib().iemic_shifted_jacobian(self._h, float(sigma)), "iemic_shifted_jacobian")
 
-    def eigs(self, k: int = 6, sigma: float = 0.0, m: int = 40, tol: float = 1e-8, seed: int = 1):
+    def eigs(self, k: int = 6, sigma: float = 0.0, m: int = 40, tol: float = 1e-8, seed: int = 1,
+             restarts: int = 0, keep: int = None):
         """The k eigenvalues of J x = lambda B x nearest the real shift sigma at the current
-        state, with eigenvectors, by unrestarted shift-invert Arnoldi of at most m steps
-        (m <= 64) on (J - sigma B)^-1 B -> iemic.eigs.EigResult.
+        state, with eigenvectors, by shift-invert Arnoldi with a basis of at most m vectors
+        (m <= 64) on (J - sigma B)^-1 B and up to `restarts` thick (Krylov-Schur) restarts
+        -> iemic.eigs.EigResult.
+
+        restarts = 0 (the default) is the unrestarted run of at most m steps.  With
+        restarts > 0, a run that reaches m steps with a wanted pair above tol keeps the
+        invariant subspace of its `keep` Ritz values of largest |theta| (default k + 3, capped
+        at m - 1 and 16; k <= keep; a conjugate pair is never split: one more, or one fewer at
+        the cap), compresses the basis onto it in one pass on the device, and goes on stepping
+        from there; no inner solve is repeated.  A run that converges before step m is the
+        same, bit for bit, whatever `restarts` is.  EigResult.steps counts the inner solves of
+        the whole run, EigResult.restarts the restarts performed.
 
         After every step from k on the leading Hessenberg block is decomposed
         (numpy.linalg.eig); the run stops when the k Ritz pairs of largest |theta| all have
@@ -717,7 +728,7 @@ class Ocean:
         Jacobian is left shifted and the preconditioner is that of J - sigma B: the next
         computeJacobian restores J and the next solve refactors."""
         from . import eigs as _eigs
-        return _eigs.eigs(self, k=k, sigma=sigma, m=m, tol=tol, seed=seed)
+        return _eigs.eigs(self, k=k, sigma=sigma, m=m, tol=tol, seed=seed, restarts=restarts, keep=keep)
 
     # ---- inspection -----------------------------------------------------------------
     def exportCSR(self):

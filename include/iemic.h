@@ -454,6 +454,18 @@ int iemic_eigs_step(iemic_ctx* ctx, const iemic_krylov* opt, double* hcol, iemic
  * host (columns alternating the real and imaginary parts of the wanted pairs), 1 <= p <= 16;
  * xvecs: p device vectors from iemic_vec_alloc, overwritten on the owned rows. */
 int iemic_eigs_ritz(iemic_ctx* ctx, int j, int p, const double* Y, void** xvecs);
+/* Thick (Krylov-Schur) restart of the run in progress: V[:, :p] <- V[:, :j] Q, V[:, p] <- V[:, j],
+ * j <- p, in place, in one pass over the basis.  After j steps the run holds A V_j = V_j G +
+ * v_{j+1} g^T with the caller's (j + 1) x j Rayleigh matrix [[G], [g^T]] (the Hessenberg matrix
+ * until the first restart).  Q: j x p row-major, host, orthonormal columns spanning an invariant
+ * subspace of G (not checked beyond finiteness); the caller replaces its matrix by
+ * [[Q^T G Q], [(Q^T g)^T]] and goes on with iemic_eigs_step, which returns full columns (the
+ * matrix is no longer Hessenberg) and may again take steps until j = m.  The next right-hand
+ * side is rebuilt from the moved vector, so iemic_eigs_ritz and iemic_eigs_residual calls since
+ * the last step do no harm.  1 <= p < j, p <= 16.  IEMIC_ESTATE outside a run or after a
+ * breakdown; IEMIC_EINVAL for p < 1, p >= j, p > 16, a null Q or a non-finite entry of Q, each
+ * by name and before anything is launched. */
+int iemic_eigs_restart(iemic_ctx* ctx, int p, const double* Q);
 /* out[0] = ||(J - sigma B) x - (lambda - sigma) B x||, out[1] = ||(J - sigma B) x|| for the
  * pair lambda = lam_re + i lam_im, x = x_re + i x_im (device vectors; x_im NULL for a real
  * pair), with the run's sigma on the run's shifted Jacobian; sums over the ranks, bit-wise
