@@ -7,7 +7,10 @@
  * ts_mg.hip, ts_mg_setup.hip) for tests/test_gpu_ts_mg.py, its entry launch and the packed
  * operand's switch (iemic_test_ts_mg_entry, iemic_test_ts_mg_nopack) for
  * tests/test_gpu_ts_entry_pack.py, and the Ritz-vector and residual
- * kernels of the stability analysis (eigs.hip) for tests/test_gpu_eigs.py.  They are exported from the
+ * kernels of the stability analysis (eigs.hip) for tests/test_gpu_eigs.py, and the active set with its
+ * tile descriptors, the compressed SpMV beside the full one and the dynamics defect
+ * (iemic_test_active_set, iemic_test_spmv_c, iemic_test_dyn_defect; active_set.hip, spmv.hip) for
+ * tests/test_gpu_spmv_tiles.py.  They are exported from the
  * device library but are NOT part of its public ABI (include/iemic.h, IEMIC_ABI_VERSION):
  * tests/dense_hooks.py binds them.  All pointers are host pointers; every hook runs on the
  * context's stream, owns its device buffers and returns the usual IEMIC_* codes.
@@ -123,6 +126,27 @@ int iemic_test_eig_compress_cost(iemic_ctx* ctx, int j, int p, int nrep, double*
  * x|^2, sum |a|^2 with a = ar + i ai, x = xr + i xi, mu = mu_r + i mu_i; ai = xi = NULL: real. */
 int iemic_test_eig_residual(iemic_ctx* ctx, int64_t N, const double* ar, const double* ai, const double* xr,
                             const double* xi, const double* B, double mu_r, double mu_i, double* out2);
+
+/* The active set of the block Gauss-Seidel set-up (ActiveSet, one rank): counts = nact, natile,
+ * ric; act (nact ints, may be NULL): the active cells as owned cells; atl (8 natile ints, may be
+ * NULL): the compressed SpMV's tile records as act_tiles wrote them. */
+int iemic_test_active_set(iemic_ctx* ctx, int64_t* counts, int* act, int* atl);
+
+/* The compressed SpMV and the full one on the same device x (one rank).  x (reference order) is
+ * staged as iemic_spmv stages it, halo exchange included, after what a solve runs before its
+ * first SpMV (gs_refresh: the stream is repacked after a new Jacobian); IEMIC_ESTATE when a solve
+ * would not take the compressed basis.  yc (6 nact doubles): spmv_kernel_c's result, written into
+ * a device buffer with 64 guard doubles before and after it, all NaN bit patterns first;
+ * *guard_changed: 1 when a guard double no longer holds that pattern.  y (reference order):
+ * spmv_kernel's result, its device buffer NaN bit patterns first. */
+int iemic_test_spmv_c(iemic_ctx* ctx, const double* x, double* yc, double* y, int* guard_changed);
+
+/* The dynamics defect alone (spmv_dyn_defect, one rank): z and rr are component-planar vectors of
+ * NE = 6 x ext cells doubles, as iemic_test_ts_mg_entry takes them; d (NE doubles) = rr - A z on
+ * the active cells' U/V/W/P rows with the context's own identity flags, from a device buffer of
+ * NaN bit patterns (what the kernel does not write comes back as such).  The hook's buffers are
+ * its own: none of the preconditioner's work vectors is touched. */
+int iemic_test_dyn_defect(iemic_ctx* ctx, int64_t NE, const double* z, const double* rr, double* d);
 
 #ifdef __cplusplus
 }

@@ -1,9 +1,10 @@
 /*
  * test_hooks.hip -- the dense solvers of the preconditioner, the coupled model's block
  * Gauss-Seidel preconditioner and the DCGS2 update pass driven on their own, and the T/S
- * multigrid's plan and levels read back (test_hooks.h).
+ * multigrid's plan and levels read back, the active set read back and the compressed SpMV and
+ * the dynamics defect driven on their own (test_hooks.h).
  * No kernels here: every hook stages host data, calls the production entry points of
- * schur_cr.hip / band_lu.hip / coupled.hip / krylov.hip on the context's stream and copies
+ * schur_cr.hip / band_lu.hip / coupled.hip / krylov.hip / spmv.hip on the context's stream and copies
  * back.
  */
 #include <algorithm>
@@ -443,4 +444,84 @@ extern "C" int iemic_test_eig_residual(iemic_ctx* c, int64_t N, const double* ar
         if ((rc = h2d(c, d.p + (int64_t)q * N, src[q], sizeof(double) * N))) return rc;
     return eigs_residual_sums(c, d.p, ai ? d.p + 3 * N : nullptr, d.p + N, ai ? d.p + 4 * N : nullptr, d.p + 2 * N,
                               mu_r, mu_i, N, out2);
+}
+
+namespace iemic {
+/* spmv.hip; prec_gs.hip, its caller, declares it for itself */
+int spmv_dyn_defect(iemic_ctx* c, const double* z, const double* r, const uint8_t* knP, double* d, bool halo);
+}  // namespace iemic
+
+extern "C" int iemic_test_active_set(iemic_ctx* c, int64_t* counts, int* act, int* atl)
+{
+    if (!c || !counts) return bad("null argument");
+    if (c->sub.nranks != 1) return bad("a single-rank context is needed");
+    const ActiveSet& as = c->gs.act;
+    if (!c->gs.ready || c->gs.kind != 2 || !as.act.p || !as.atl.p) return bad("no block Gauss-Seidel set up");
+    if (hipSetDevice(c->device) != hipSuccess) return IEMIC_EDEVICE;
+    counts[0] = as.nact;
+    counts[1] = as.natile;
+    counts[2] = as.ric;
+    int rc;
+    if (act && (rc = d2h(c, act, as.act.p, sizeof(int) * as.nact))) return rc;
+    if (atl && (rc = d2h(c, atl, as.atl.p, sizeof(int) * 8 * as.natile))) return rc;
+    return 0;
+}
+
+extern "C" int iemic_test_spmv_c(iemic_ctx* c, const double* x, double* yc, double* y, int* guard_changed)
+{
+    if (!c || !x || !yc || !y || !guard_changed) return bad("null argument");
+    if (c->sub.nranks != 1) return bad("a single-rank context is needed");
+    if (hipSetDevice(c->device) != hipSuccess) return IEMIC_EDEVICE;
+    StreamGuard guard{c};
+    const BlockGS& gs = c->gs;
+    int rc;
+    /* what fgmres does before its first SpMV, and its test for the compressed basis */
+    if ((rc = gs_refresh(c))) return rc;
+    if (!(gs.ready && gs.kind == 2 && gs.act.nact > 0 && gs.act.cmap.p && gs.act.cmp_ok && gs.act.spc.p && gs.act.atl.p)) {
+        set_error("test hook: a solve would not take the compressed SpMV");
+        return IEMIC_ESTATE;
+    }
+    constexpr size_t G = 64;                 /* guard doubles on either side of the compressed result */
+    const size_t NE = (size_t)c->sub.nerows(), NC = (size_t)NUN * gs.act.nact;
+    DevBuf<double> xd, yd, ycd;
+    if (xd.alloc(NE) || yd.alloc(NE) || ycd.alloc(NC + 2 * G)) return IEMIC_ENOMEM;
+    /* x as iemic_spmv stages it: reference order -> ext layout (halo 0), then the exchange */
+    std::vector<double> e(NE, 0.0);
+    c->su.ref_to_ext(x, e.data());
+    if ((rc = h2d(c, xd.p, e.data(), sizeof(double) * NE))) return rc;
+    if ((rc = halo_exchange(c, xd.p, 1))) return rc;
+    HIP_OK(hipMemsetAsync(yd.p, 0xff, sizeof(double) * NE, c->stream));
+    HIP_OK(hipMemsetAsync(ycd.p, 0xff, sizeof(double) * (NC + 2 * G), c->stream));
+    if ((rc = spmv_kernel_c(c, xd.p, ycd.p + G))) return rc;
+    if ((rc = spmv_kernel(c, xd.p, yd.p))) return rc;
+    std::vector<double> hc(NC + 2 * G);
+    if ((rc = d2h(c, hc.data(), ycd.p, sizeof(double) * hc.size()))) return rc;
+    if ((rc = d2h(c, e.data(), yd.p, sizeof(double) * NE))) return rc;
+    std::vector<unsigned char> fill(sizeof(double) * G, 0xff);
+    *guard_changed = (std::memcmp(hc.data(), fill.data(), fill.size()) != 0 ||
+                      std::memcmp(hc.data() + G + NC, fill.data(), fill.size()) != 0) ? 1 : 0;
+    std::memcpy(yc, hc.data() + G, sizeof(double) * NC);
+    c->su.ext_to_ref(e.data(), y);
+    return 0;
+}
+
+extern "C" int iemic_test_dyn_defect(iemic_ctx* c, int64_t NE, const double* z, const double* rr, double* d)
+{
+    if (!c || !z || !rr || !d) return bad("null argument");
+    if (c->sub.nranks != 1) return bad("a single-rank context is needed");
+    const BlockGS& gs = c->gs;
+    if (!gs.ready || gs.kind != 2 || !gs.knP.p || !gs.act.vp) return bad("no block Gauss-Seidel set up");
+    if (NE != c->sub.nerows()) return bad("vector length");
+    if (hipSetDevice(c->device) != hipSuccess) return IEMIC_EDEVICE;
+    StreamGuard guard{c};
+    /* buffers of the hook's own: the preconditioner's work vectors are left as they are */
+    DevBuf<double> zd, rd, dd;
+    if (zd.alloc(NE) || rd.alloc(NE) || dd.alloc(NE)) return IEMIC_ENOMEM;
+    int rc;
+    if ((rc = h2d(c, zd.p, z, sizeof(double) * NE))) return rc;
+    if ((rc = h2d(c, rd.p, rr, sizeof(double) * NE))) return rc;
+    HIP_OK(hipMemsetAsync(dd.p, 0xff, sizeof(double) * NE, c->stream));
+    if ((rc = spmv_dyn_defect(c, zd.p, rd.p, gs.knP.p, dd.p, false))) return rc;
+    HIP_OK(hipGetLastError());
+    return d2h(c, d, dd.p, sizeof(double) * NE);
 }

@@ -1,7 +1,8 @@
 """ctypes binding of the device library's test hooks (i-emic_amd/csrc/test_hooks.h): the
 block cyclic reduction, the batched Gauss-Jordan inverse and the band LU of the
-preconditioner, each driven on its own, and the T/S multigrid's plan, levels and fusion
-switch.  Not part of the public ABI (include/iemic.h)."""
+preconditioner, each driven on its own, the T/S multigrid's plan, levels and fusion
+switch, and the active set, the compressed SpMV and the dynamics defect.  Not part of the
+public ABI (include/iemic.h)."""
 import ctypes as C
 
 import numpy as np
@@ -35,6 +36,12 @@ def hooks():
         L.iemic_test_ts_mg_level.argtypes = [vp, i] + [_PD] * 5
         L.iemic_test_ts_mg_nofuse.restype = i
         L.iemic_test_ts_mg_nofuse.argtypes = [vp, i]
+        L.iemic_test_active_set.restype = i
+        L.iemic_test_active_set.argtypes = [vp, C.POINTER(C.c_int64), _PI, _PI]
+        L.iemic_test_spmv_c.restype = i
+        L.iemic_test_spmv_c.argtypes = [vp, _PD, _PD, _PD, _PI]
+        L.iemic_test_dyn_defect.restype = i
+        L.iemic_test_dyn_defect.argtypes = [vp, C.c_int64, _PD, _PD, _PD]
         _bound = L
     return _bound
 
@@ -153,6 +160,47 @@ def ts_mg_level(h, q, n, m, l, coarsest):
     if rc:
         raise RuntimeError(f"iemic_test_ts_mg_level: {rc} {last_error()}")
     return off.reshape(16, ncl), diag.reshape(4, ncl), b, z, None if cinv is None else cinv.reshape(2 * ncl, 2 * ncl)
+
+
+def active_set(h):
+    """the active set of context h's block GS set-up -> (nact, natile, ric, act (nact,),
+    atl (natile, 8)); act: owned cells, atl: the compressed SpMV's tile records"""
+    cnt = np.zeros(3, dtype=np.int64)
+    p64 = cnt.ctypes.data_as(C.POINTER(C.c_int64))
+    rc = hooks().iemic_test_active_set(h, p64, None, None)
+    if rc:
+        raise RuntimeError(f"iemic_test_active_set: {rc} {last_error()}")
+    nact, natile, ric = (int(v) for v in cnt)
+    act = np.full(max(nact, 1), -1, dtype=np.int32)
+    atl = np.full(8 * max(natile, 1), -1, dtype=np.int32)
+    rc = hooks().iemic_test_active_set(h, p64, act.ctypes.data_as(_PI), atl.ctypes.data_as(_PI))
+    if rc:
+        raise RuntimeError(f"iemic_test_active_set: {rc} {last_error()}")
+    return nact, natile, ric, act[:nact], atl[:8 * natile].reshape(natile, 8)
+
+
+def spmv_c(h, x, nact):
+    """k_spmv7c and k_spmv7 on the same device x (reference order) -> (yc (6 nact,), y
+    (reference order), guard_changed); NaN where a kernel wrote nothing"""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    yc, y = np.full(6 * nact, np.nan), np.full(x.size, np.nan)
+    g = C.c_int(-1)
+    rc = hooks().iemic_test_spmv_c(h, _d(x), _d(yc), _d(y), C.byref(g))
+    if rc:
+        raise RuntimeError(f"iemic_test_spmv_c: {rc} {last_error()}")
+    return yc, y, g.value
+
+
+def dyn_defect(h, z, rr):
+    """spmv_dyn_defect on component-planar z, rr (6 x ext cells) -> d, NaN where unwritten"""
+    z = np.ascontiguousarray(z, dtype=np.float64)
+    rr = np.ascontiguousarray(rr, dtype=np.float64)
+    assert z.size == rr.size
+    d = np.full(z.size, np.nan)
+    rc = hooks().iemic_test_dyn_defect(h, z.size, _d(z), _d(rr), _d(d))
+    if rc:
+        raise RuntimeError(f"iemic_test_dyn_defect: {rc} {last_error()}")
+    return d
 
 
 def ts_mg_nofuse(h, on):
