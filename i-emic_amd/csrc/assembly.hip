@@ -326,6 +326,7 @@ int compute_forcing(iemic_ctx* c)
     hipLaunchKernelGGL(k_forcing, dim3((unsigned)((c->sub.nloc + 255) / 256)), dim3(256), 0,
                        c->stream, g, c->d_ftab.p, c->d_qcor.p, c->d_frc.p, c->sub.nloc);
     HIP_OK(hipGetLastError());
+    c->frc_gen++;
     return 0;
 }
 

@@ -355,6 +355,16 @@ struct Theta {
     DevBuf<double> Ft, b;            /* F_theta(x) and F_theta / dt / theta (the solve's rhs) */
 };
 
+/* The stochastic theta model's state (stochastic.hip; StochasticThetaModel.H's B_ and G_), surface
+ * fields of the owned cells, [(j - jb0) nx + (i - ib0)], allocated at the first use */
+struct Stoch {
+    DevBuf<double> coF;              /* the forcing column: forcing_cell's f[SS] with SPER = 0 */
+    DevBuf<double> G;                /* the noise of the armed step                        */
+    DevBuf<double> pert;             /* its m normals, global latitude index               */
+    int64_t gen = -1;                /* iemic_ctx::frc_gen when coF was computed (-1: never) */
+    int armed = 0;                   /* theta_rhs adds G (iemic_theta_init_step_noise)     */
+};
+
 /* A shift-invert Arnoldi run (eigs.hip): the basis of (J - sigma B)^-1 B and its work vectors,
  * ext layout, allocated by eigs_begin and freed by eigs_end */
 struct Eigs {
@@ -442,6 +452,8 @@ struct iemic_ctx {
     iemic::BlockGS gs;
     iemic::Krylov kr;
     iemic::Theta th;
+    iemic::Stoch st;
+    int64_t frc_gen = 0;             /* counts compute_forcing: what Stoch::coF was made from */
     iemic::Eigs eg;
     iemic::Geo geo() const;
     iemic_ctx() = default;
@@ -664,6 +676,16 @@ int theta_jacobian(iemic_ctx* c);
 /* state -= dx on the owned rows; *absmax: this rank's max |dx| (NaN propagates) */
 int theta_update(iemic_ctx* c, const double* dx, double* absmax);
 int theta_restore(iemic_ctx* c);
+/* stochastic.hip: the stochastic theta model (StochasticThetaModel.H) on top of theta.hip */
+/* Stoch::coF of the current forcing (d_frc and par untouched) */
+int stoch_forcing(iemic_ctx* c);
+/* Stoch::coF as the reference's matrix: owned entries in row order (pointers may be null) */
+int stoch_export(iemic_ctx* c, int64_t* rows, int* cols, double* vals, int64_t* nnz);
+/* after theta_init_step: coF again if the forcing changed, G = (sqrt(dt) sigma) (coF pert[j]),
+ * noise armed (sigma = 0: nothing armed) */
+int stoch_arm(iemic_ctx* c, double sigma, const double* pert);
+/* theta_rhs's residual launch while noise is armed: F_theta + G into Theta::Ft, scaled into Theta::b */
+int stoch_theta_residual(iemic_ctx* c);
 /* eigs.hip: shift-invert Arnoldi for J x = lambda B x on the resident state */
 /* J(state) with -(sigma B) on the diagonal of the U, V, T and S rows (sigma = 0: J untouched) */
 int shifted_jacobian(iemic_ctx* c, double sigma);

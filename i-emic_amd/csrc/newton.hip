@@ -1,7 +1,7 @@
 /*
  * newton.hip -- the C ABI's solve side: the operator (F, J, SpMV), the preconditioner and the
- * linear solves, the Newton iteration, and the entry points of the theta stepper (theta.hip) and
- * of the linear stability analysis (eigs.hip).
+ * linear solves, the Newton iteration, and the entry points of the theta stepper (theta.hip), of
+ * its stochastic model (stochastic.hip) and of the linear stability analysis (eigs.hip).
  *
  * One iteration of transient/Newton.H:92-99 is written once, newton_iterate, over the two
  * models that run it: the steady model (F(x) = 0, iemic_newton_step) and the theta model of a
@@ -274,6 +274,51 @@ extern "C" int iemic_theta_newton_step(iemic_ctx* c, const iemic_krylov* opt, in
     CTX_CHECK(c);
     if (!opt) return IEMIC_EINVAL;
     return newton_iterate(c, opt, ThetaModel{refactor}, info);
+}
+
+/* ---- the stochastic theta model (stochastic.hip) ----------------------------------------- */
+/* Ocean::computeForcing (THCM::computeForcing, THCM.C:836-940) */
+extern "C" int iemic_forcing_compute(iemic_ctx* c)
+{
+    CTX_CHECK(c);
+    return stoch_forcing(c);
+}
+
+/* Ocean::getForcing: the entries of the last iemic_forcing_compute */
+extern "C" int iemic_forcing_export(iemic_ctx* c, int64_t* rows, int* cols, double* vals, int64_t* nnz)
+{
+    CTX_CHECK(c);
+    if (!nnz) {
+        set_error("iemic_forcing_export: nnz is NULL");
+        return IEMIC_EINVAL;
+    }
+    if (c->st.gen < 0) {
+        set_error("iemic_forcing_export: no forcing operator computed (iemic_forcing_compute)");
+        return IEMIC_ESTATE;
+    }
+    return stoch_export(c, rows, cols, vals, nnz);
+}
+
+/* StochasticThetaModel::initStep (StochasticThetaModel.H:52-72) with the caller's normals */
+extern "C" int iemic_theta_init_step_noise(iemic_ctx* c, double dt, double theta, double sigma,
+                                           const double* pert)
+{
+    CTX_CHECK(c);
+    if (!pert) {
+        set_error("iemic_theta_init_step_noise: pert is NULL (m standard normals, one per latitude)");
+        return IEMIC_EINVAL;
+    }
+    if (!std::isfinite(sigma) || sigma < 0.0) {
+        set_error("iemic_theta_init_step_noise: sigma must be finite and >= 0");
+        return IEMIC_EINVAL;
+    }
+    for (int j = 0; j < c->m; j++)
+        if (!std::isfinite(pert[j])) {
+            set_error("iemic_theta_init_step_noise: pert[" + std::to_string(j) + "] is not finite");
+            return IEMIC_EINVAL;
+        }
+    const int rc = theta_init_step(c, dt, theta);
+    return rc ? rc : stoch_arm(c, sigma, pert);
 }
 
 /* ---- linear stability analysis (eigs.hip): the JDQZInterface seam ------------------------ */

@@ -77,6 +77,7 @@ class Ocean {
         check(iemic_create(&ctx_, &grid, landm.data()), "iemic_create");
         N_ = (size_t)iemic_nrows(ctx_);
         nm_ = (size_t)grid.n * grid.m;
+        m_ = (size_t)grid.m;
         state_ = std::make_shared<Vector>(N_);
         rhs_ = std::make_shared<Vector>(N_);
         sol_ = std::make_shared<Vector>(N_);
@@ -234,6 +235,35 @@ class Ocean {
         return info;
     }
 
+    /* ---- the stochastic theta model: what StochasticThetaModel<Ocean> adds ----------- */
+    /* Ocean::computeForcing: the stochastic forcing operator of the current parameters */
+    void computeForcing() { check(iemic_forcing_compute(ctx_), "computeForcing"); }
+    /* Ocean::getForcing: the operator's entries (row, column = latitude j, value), sorted by row */
+    struct Forcing {
+        std::vector<int64_t> rows;
+        std::vector<int> cols;
+        std::vector<double> vals;
+    };
+    Forcing getForcing()
+    {
+        int64_t nnz = 0;
+        check(iemic_forcing_export(ctx_, nullptr, nullptr, nullptr, &nnz), "getForcing");
+        Forcing f{std::vector<int64_t>((size_t)nnz), std::vector<int>((size_t)nnz), std::vector<double>((size_t)nnz)};
+        check(iemic_forcing_export(ctx_, f.rows.data(), f.cols.data(), f.vals.data(), &nnz), "getForcing");
+        return f;
+    }
+    /* StochasticThetaModel::initStep (StochasticThetaModel.H:52-72): thetaInitStep, then the
+     * step's noise G = (sqrt(dt) sigma) (B_f pert) armed for thetaRHS / thetaNewtonStep; pert: m
+     * standard normals, one per latitude (the caller's generator) */
+    void stochasticInitStep(double dt, double theta, double sigma, const std::vector<double>& pert)
+    {
+        if (pert.size() != m_)
+            throw std::runtime_error("stochasticInitStep: pert has " + std::to_string(pert.size()) +
+                                     " entries, the grid has " + std::to_string(m_) + " latitudes");
+        check(iemic_theta_init_step_noise(ctx_, dt, theta, sigma, pert.data()), "stochasticInitStep");
+        preProcess();
+    }
+
     /* ---- linear stability analysis: the calls a JDQZInterface-shaped eigen-solver makes
      * (src/utils/JDQZInterface.H); the Hessenberg eigen-decomposition is the caller's
      * (INTEGRATION.md shows it with LAPACKE_dhseqr / dtrevc) ------------------------- */
@@ -276,7 +306,7 @@ class Ocean {
 
   private:
     iemic_ctx* ctx_ = nullptr;
-    size_t N_ = 0, nm_ = 0;
+    size_t N_ = 0, nm_ = 0, m_ = 0;
     std::shared_ptr<Vector> state_, rhs_, sol_;
     iemic_krylov krylov_{};
     iemic_solve_info lastSolve_{};

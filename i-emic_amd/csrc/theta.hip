@@ -102,6 +102,7 @@ int theta_init_step(iemic_ctx* c, double dt, double theta)
         }
     }
     th.init = 0;
+    c->st.armed = 0;                 /* a plain step carries no noise (stoch_arm arms after this) */
     int rc = halo_exchange(c, c->d_x.p, HALO);
     if (rc) return rc;
     if ((rc = assemble_rhs(c, c->d_x.p, c->d_F.p))) return rc;
@@ -114,7 +115,8 @@ int theta_init_step(iemic_ctx* c, double dt, double theta)
     return 0;
 }
 
-/* ThetaModel::computeRHS (ThetaModel.H:87-113) */
+/* ThetaModel::computeRHS (ThetaModel.H:87-113); with noise armed for the step,
+ * StochasticThetaModel::computeRHS (stochastic.hip) */
 int theta_rhs(iemic_ctx* c)
 {
     int rc = theta_ready(c, "iemic_theta_rhs");
@@ -122,6 +124,7 @@ int theta_rhs(iemic_ctx* c)
     Theta& th = c->th;
     if ((rc = halo_exchange(c, c->d_x.p, HALO))) return rc;
     if ((rc = assemble_rhs(c, c->d_x.p, c->d_F.p))) return rc;
+    if (c->st.armed) return stoch_theta_residual(c);
     const auto [o, NL, G] = owned(c);
     hipLaunchKernelGGL(k_theta_residual, dim3(G), dim3(256), 0, c->stream, th.dt * th.theta, c->d_F.p + o,
                        th.dt * (1 - th.theta), th.Fold.p + o, c->d_B.p + o, th.xold.p + o, c->d_x.p + o, th.dt,

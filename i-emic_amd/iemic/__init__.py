@@ -9,7 +9,7 @@ from .config import THCMConfig, landmask, preset, synthetic_state
 from ._lib import IemicError
 
 __all__ = ["config", "THCMConfig", "landmask", "preset", "synthetic_state", "IemicError",
-           "Ocean", "ThetaStepper"]
+           "Ocean", "ThetaStepper", "StochasticThetaStepper"]
 
 
 def __getattr__(name):
@@ -19,4 +19,7 @@ def __getattr__(name):
     if name == "ThetaStepper":
         from .transient import ThetaStepper
         return ThetaStepper
+    if name == "StochasticThetaStepper":
+        from .transient import StochasticThetaStepper
+        return StochasticThetaStepper
     raise AttributeError(name)

@@ -16,7 +16,7 @@ PKG_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(PKG_DIR, "lib", os.environ.get("IEMIC_LIB", "libiemic_amd.so"))
 
 IEMIC_ENODEV = -19
-ABI_VERSION = 9             # IEMIC_ABI_VERSION of include/iemic.h this binding mirrors
+ABI_VERSION = 10            # IEMIC_ABI_VERSION of include/iemic.h this binding mirrors
 IEMIC_ENOCONV = 1           # iemic_newton_step: applied, but the solve missed its tolerance
 
 
@@ -180,6 +180,9 @@ def lib():
         "iemic_theta_jacobian": (C.c_int, [vp]),
         "iemic_theta_restore": (C.c_int, [vp]),
         "iemic_theta_newton_step": (C.c_int, [vp, P(Krylov), C.c_int, P(ThetaInfo)]),
+        "iemic_forcing_compute": (C.c_int, [vp]),
+        "iemic_forcing_export": (C.c_int, [vp, P64, PI, PD, P64]),
+        "iemic_theta_init_step_noise": (C.c_int, [vp, C.c_double, C.c_double, C.c_double, PD]),
         "iemic_shifted_jacobian": (C.c_int, [vp, C.c_double]),
         "iemic_eigs_begin": (C.c_int, [vp, C.c_double, C.c_int, C.c_uint64, P(Krylov)]),
         "iemic_eigs_step": (C.c_int, [vp, P(Krylov), PD, P(EigsInfo)]),
@@ -267,6 +270,7 @@ EXPORTED = ("iemic_abi_version", "iemic_create", "iemic_create_dist", "iemic_com
             "iemic_spmv_dev", "iemic_prec_compute", "iemic_prec_apply", "iemic_solve",
             "iemic_solve_dev", "iemic_newton_step", "iemic_theta_init_step", "iemic_theta_rhs",
             "iemic_theta_jacobian", "iemic_theta_restore", "iemic_theta_newton_step",
+            "iemic_forcing_compute", "iemic_forcing_export", "iemic_theta_init_step_noise",
             "iemic_shifted_jacobian", "iemic_eigs_begin", "iemic_eigs_step", "iemic_eigs_ritz",
             "iemic_eigs_restart", "iemic_eigs_residual", "iemic_eigs_end", "iemic_vec_alloc", "iemic_vec_free",
             "iemic_vec_update", "iemic_vec_dot", "iemic_vec_norm_inf", "iemic_vec_from_ref",

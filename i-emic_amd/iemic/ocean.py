@@ -691,6 +691,42 @@ class Ocean:
             self.solve_hook(info.solve)
         return info
 
+    # ---- the stochastic theta model (StochasticThetaModel<Ocean>; iemic.transient) ------
+    def computeForcing(self) -> None:
+        """Ocean::computeForcing (THCM.C:836-940; stochastic_forcing, forcing.F90:220-265): the
+        stochastic forcing operator of the current parameters and inserted fields, one entry per
+        surface cell: its S forcing with par(SPER) = 0.  The model's own forcing and SPER are
+        untouched.  With "Coupled Salinity" the operator is empty."""
+        check(lib().iemic_forcing_compute(self._h), "iemic_forcing_compute")
+
+    def getForcing(self):
+        """Ocean::getForcing: (rows, cols, vals) of the last computeForcing, the entries this
+        rank owns sorted by row (like exportCSR, a rank's part; bands concatenate in rank
+        order), in the reference's numbering: row 6 ((k m + j) n + i) + 5 at k = l - 1, column
+        j.  The land cells' values are the reference's; the integral-condition row is absent."""
+        nnz = C.c_int64()
+        check(lib().iemic_forcing_export(self._h, None, None, None, C.byref(nnz)), "iemic_forcing_export")
+        rows = np.zeros(nnz.value, dtype=np.int64)
+        cols = np.zeros(nnz.value, dtype=np.int32)
+        vals = np.zeros(nnz.value)
+        check(lib().iemic_forcing_export(self._h, ptr(rows, C.c_int64), ptr(cols, C.c_int), ptr(vals),
+                                         C.byref(nnz)), "iemic_forcing_export")
+        return rows, cols, vals
+
+    def stochasticInitStep(self, dt: float, theta: float, sigma: float, pert) -> None:
+        """StochasticThetaModel::initStep (StochasticThetaModel.H:52-72): thetaInitStep, then the
+        step's noise G = (sqrt(dt) sigma) (B_f pert) on the surface S rows of the ocean cells,
+        added to F_theta by thetaRHS and thetaNewtonStep until the next init step (thetaInitStep
+        disarms it).  pert: m standard normals, one per latitude, the same on every rank.
+        sigma = 0 is thetaInitStep bit for bit; sigma < 0, a non-finite sigma or pert entry and
+        a pert of another length raise IemicError by name."""
+        pert = np.ascontiguousarray(pert, dtype=np.float64).reshape(-1)
+        if pert.size != self.cfg.m:
+            raise IemicError(f"stochasticInitStep: pert has {pert.size} entries, the grid has "
+                             f"{self.cfg.m} latitudes")
+        check(lib().iemic_theta_init_step_noise(self._h, float(dt), float(theta), float(sigma), ptr(pert)),
+              "iemic_theta_init_step_noise")
+
     # ---- linear stability analysis (the JDQZInterface seam; iemic.eigs) -----------------
     def shiftedJacobian(self, sigma: float) -> None:
         """J - sigma B at the current state (J is assembled first); exportCSR, applyMatrix,

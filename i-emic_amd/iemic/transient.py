@@ -18,12 +18,17 @@ only through
 (and ``postProcess`` / ``saveStateToFile`` where the model has them), so a CPU model with the
 same surface can stand in for ``iemic.ocean.Ocean``.  Parameter names and defaults are the
 reference's (AdaptiveTransient.H:60-68, Newton.H:50-51, ThetaModel.H:37,
-Transient.hpp:138-145).  The stochastic theta models, AMS / TAMS / GPA and CoupledThetaModel
-are not restated.
+Transient.hpp:138-145).
+
+``StochasticThetaStepper`` is the same loop on ``StochasticThetaModel<Ocean>``
+(StochasticThetaModel.H): every step starts with ``stochasticInitStep(dt, theta, sigma, pert)``
+in place of ``thetaInitStep``, with m fresh standard normals.  The projected stochastic model,
+AMS / TAMS / GPA, their score functions and CoupledThetaModel are not restated.
 """
 from __future__ import annotations
 
 import math
+import os
 from dataclasses import dataclass
 
 import numpy as np
@@ -60,11 +65,13 @@ class TransientRecord:
 class ThetaStepper:
     """AdaptiveTransient<ThetaModel<Model>>: ``run()`` steps the model from its current state."""
 
+    defaults = DEFAULTS
+
     def __init__(self, model, params=None):
-        p = dict(DEFAULTS)
+        p = dict(self.defaults)
         for k, v in (params or {}).items():
-            if k not in DEFAULTS and k not in _DERIVED:
-                raise KeyError(f"ThetaStepper: unknown parameter {k!r}")
+            if k not in self.defaults and k not in _DERIVED:
+                raise KeyError(f"{type(self).__name__}: unknown parameter {k!r}")
             p[k] = v
         self.model = model
         self.params = p
@@ -125,6 +132,10 @@ class ThetaStepper:
                 return
             self.newton_steps += 1
 
+    def _init_step(self) -> None:
+        """The model call that starts a time step (ThetaModel::initStep), also after a rejected one."""
+        self.model.thetaInitStep(self.dt, self.theta)
+
     def run(self) -> int:
         """AdaptiveTransient::run (AdaptiveTransient.H:88-171).  Returns 0, or 1 when a Newton
         run failed at the minimum time step or with adaptivity off."""
@@ -132,7 +143,7 @@ class ThetaStepper:
         self.time, self.time_steps = 0.0, 0
         while self.time < self.tmax and (self.nsteps < 0 or self.time_steps < self.nsteps):
             m.preProcess()
-            m.thetaInitStep(self.dt, self.theta)
+            self._init_step()
             self._newton()
             if not self.converged:
                 m.thetaRestore()
@@ -156,3 +167,68 @@ class ThetaStepper:
                 self.dt = max(self.dt / self.decrease, self.dt_min)
             self._total += self.newton_steps
         return 0
+
+
+class StochasticThetaStepper(ThetaStepper):
+    """AdaptiveTransient<StochasticThetaModel<Model>>: the theta stepper with noise on the
+    salinity flux.  The model adds ``stochasticInitStep(dt, theta, sigma, pert)`` to the surface
+    ThetaStepper drives and says how many latitudes it has (``cfg.m``); nothing else of the loop
+    changes, so a step the adaptive loop rejects starts again with a new draw, as the reference's
+    ``initStep`` does.
+
+    Parameters beside ThetaStepper's: "sigma" (StochasticThetaModel.H:35, default 1.0, >= 0) and
+    "noise seed" (StochasticBase; 0 takes a seed from the OS, and ``noise_seed`` holds the one in
+    use either way).  ``draws`` counts the blocks drawn: accepted plus rejected steps.
+
+    The noise of block b is ``noise_block(noise_seed, b, m)``: m standard normals from NumPy's
+    counter-based Philox generator, keyed by the seed, its counter set to the block.  A block
+    depends on (seed, b) alone: not on the blocks before it, the time steps taken or the number of
+    ranks (every rank draws the same m values; the device keeps the latitudes it owns).  This is
+    NOT the reference's stream and cannot be: there every process seeds its own ``mt19937_64``
+    and draws for the columns it holds, so the noise changes with the number of processes, and
+    ``std::normal_distribution`` is implementation-defined, so it changes with the C++ library.
+
+    ``pert_source(block, m)``, if given, replaces the generator (a rare-event driver that chooses
+    its noise; the tests).  What it returns must be m finite numbers."""
+
+    defaults = dict(DEFAULTS, **{"sigma": 1.0, "noise seed": 0})
+
+    def __init__(self, model, params=None, pert_source=None):
+        super().__init__(model, params)
+        self.sigma = float(self.params["sigma"])
+        if not (math.isfinite(self.sigma) and self.sigma >= 0.0):
+            raise ValueError(f'StochasticThetaStepper: "sigma" = {self.sigma} must be finite and >= 0')
+        seed = int(self.params["noise seed"])
+        if seed < 0:
+            raise ValueError(f'StochasticThetaStepper: "noise seed" = {seed} must be >= 0')
+        if seed == 0 and pert_source is None:
+            while seed == 0:
+                seed = int.from_bytes(os.urandom(8), "little")
+        self.noise_seed = seed
+        self.pert_source = pert_source
+        self.draws = 0
+
+    @staticmethod
+    def noise_block(seed: int, block: int, m: int) -> np.ndarray:
+        """Block ``block`` of the stream of ``seed``: m standard normals."""
+        bits = np.random.Philox(key=int(seed), counter=[0, int(block), 0, 0])
+        return np.random.Generator(bits).standard_normal(int(m))
+
+    def _pert(self) -> np.ndarray:
+        m = int(self.model.cfg.m)
+        if self.pert_source is not None:
+            pert = np.asarray(self.pert_source(self.draws, m), dtype=np.float64).reshape(-1)
+        else:
+            pert = self.noise_block(self.noise_seed, self.draws, m)
+        if pert.size != m:
+            raise ValueError(f"StochasticThetaStepper: pert has {pert.size} entries, the model has "
+                             f"{m} latitudes")
+        if not np.all(np.isfinite(pert)):
+            raise ValueError(f"StochasticThetaStepper: pert[{int(np.flatnonzero(~np.isfinite(pert))[0])}] "
+                             "is not finite")
+        self.draws += 1
+        return pert
+
+    def _init_step(self) -> None:
+        """StochasticThetaModel::initStep (StochasticThetaModel.H:52-72)"""
+        self.model.stochasticInitStep(self.dt, self.theta, self.sigma, self._pert())

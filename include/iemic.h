@@ -46,9 +46,10 @@ extern "C" {
 /* Version of this header's structs and entry points.  Bumped whenever a struct changes
  * size or meaning (5: iemic_solve_info gained `safeguard` in round 4, the device vector
  * algebra of round 5; 7: surface fluxes and inserted forcing fields; 8: the theta time stepper;
- * 9: linear stability analysis); a caller built against another header must refuse to run:
+ * 9: linear stability analysis; 10: the stochastic theta model); a caller built against another
+ * header must refuse to run:
  *   if (iemic_abi_version() != IEMIC_ABI_VERSION) abort(); */
-#define IEMIC_ABI_VERSION 9
+#define IEMIC_ABI_VERSION 10
 int iemic_abi_version(void);
 
 typedef struct iemic_ctx iemic_ctx;
@@ -410,6 +411,31 @@ typedef struct {
 } iemic_theta_info;
 int iemic_theta_newton_step(iemic_ctx* ctx, const iemic_krylov* opt, int refactor,
                             iemic_theta_info* info);
+
+/* ---- the stochastic theta model (src/transient/StochasticThetaModel.H): noise on the salinity
+ * flux.  The ocean's stochastic forcing operator B_f (Ocean::computeForcing / getForcing,
+ * THCM.C:836-940, stochastic_forcing of forcing.F90:220-265) has one entry per surface cell
+ * (i, j): the S forcing of that cell with par(SPER) = 0, in column j.  A step's noise is
+ *   G = (sqrt(dt) sigma) (B_f pert),   pert: m standard normals, one per latitude,
+ * and the step's residual is F_theta + G.  Two departures from the reference: G is zero on land
+ * cells (there it lands on identity rows), and pert is the caller's, m values in the global
+ * latitude index on every rank, so a run does not depend on the number of ranks. */
+/* Ocean::computeForcing: the operator of the current parameters and inserted fields.  The model's
+ * own forcing and parameters are untouched.  "Coupled Salinity": an empty operator, no error. */
+int iemic_forcing_compute(iemic_ctx* ctx);
+/* Ocean::getForcing: the entries of the last iemic_forcing_compute this rank owns, sorted by
+ * row, in the reference's numbering: row 6 ((k m + j) n + i) + 5 at k = l - 1, column j, 0-based.
+ * The values on land cells are the reference's (not zero); the integral-condition row (SRES = 0) is
+ * left out.  *nnz receives the count, at most the owned surface cells; rows, cols and vals may be
+ * NULL (the count alone).  IEMIC_ESTATE before iemic_forcing_compute. */
+int iemic_forcing_export(iemic_ctx* ctx, int64_t* rows, int* cols, double* vals, int64_t* nnz);
+/* StochasticThetaModel::initStep (StochasticThetaModel.H:52-72): iemic_theta_init_step, the
+ * operator again if the forcing changed since it was computed, G from pert (m doubles), and the
+ * noise armed: until the next init_step, iemic_theta_rhs and iemic_theta_newton_step work on
+ * F_theta + G.  iemic_theta_init_step disarms it.  sigma = 0 is iemic_theta_init_step bit for
+ * bit.  A NULL pert, a non-finite sigma or pert entry and sigma < 0 are refused with IEMIC_EINVAL
+ * before anything runs. */
+int iemic_theta_init_step_noise(iemic_ctx* ctx, double dt, double theta, double sigma, const double* pert);
 
 /* ---- linear stability of the state: J x = lambda B x by shift-invert Arnoldi -----------
  * The seam is the generalised eigenvalue solver the reference's drivers build on
