@@ -21,6 +21,18 @@ namespace iemic {
 
 void set_error(const std::string& s);
 
+/* Workgroups dealt to the 8 XCDs in contiguous runs.  xcd_grid: blocks launched for nwg
+ * workgroups.  xcd_block: logical workgroup of block b of such a grid: the XCDs (blocks dealt
+ * round robin, b % 8) get contiguous runs of workgroups, so tiles of neighbouring latitude
+ * rows, which read each other's rows, share an L2; -1: idle block */
+static inline unsigned xcd_grid(int64_t nwg) { return 8u * (unsigned)((nwg + 7) / 8); }
+__device__ __forceinline__ int xcd_block(int nwg)
+{
+    const int per = (nwg + 7) >> 3;
+    const int w = (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);
+    return w < nwg ? w : -1;
+}
+
 #define HIP_OK(expr)                                                                   \
     do {                                                                               \
         hipError_t e_ = (expr);                                                        \
@@ -270,7 +282,7 @@ int act_pack_streams(iemic_ctx* c);
 /* repack the coefficient copies after a new Jacobian (ActiveSet::coef_stale) */
 int gs_refresh(iemic_ctx* c);
 
-/* the plain T/S sweeps of the block GS (prec_gs.hip, ts_mg = 0); the multigrid's level 0 is
+/* the plain T/S sweeps of the block GS (ts_sweeps.hip, ts_mg = 0); the multigrid's level 0 is
  * packed from tsoff */
 struct TsSweeps {
     DevBuf<double> tsinv;            /* 2x2 T/S inverses per cell                       */
@@ -280,7 +292,7 @@ struct TsSweeps {
     DevBuf<double> bts;              /* T/S right-hand side (AoS)                        */
 };
 
-/* Preconditioner state (prec.hip: block Jacobi, prec_gs.hip: block Gauss-Seidel). */
+/* Preconditioner state (prec.hip: block Jacobi; gs_setup.hip, prec_gs.hip: block Gauss-Seidel). */
 struct BlockGS {
     int ready = 0;
     int kind = 0;                    /* 1: block-Jacobi, 2: block Gauss-Seidel           */
@@ -659,6 +671,9 @@ int intcond_correction(iemic_ctx* c, const double* x_dev);
 /* y = J x on the owned rows; x (ext layout) gets its halo rows exchanged first */
 int spmv(iemic_ctx* c, double* x, double* y, hipStream_t s);
 int spmv_kernel(iemic_ctx* c, const double* x, double* y);
+/* the block GS dynamics defect d = r - A_DD z on the active U/V/W/P rows (component-planar);
+ * halo: on the bands' two halo rows too */
+int spmv_dyn_defect(iemic_ctx* c, const double* z, const double* r, const uint8_t* knP, double* d, bool halo = false);
 double dot(iemic_ctx* c, const double* a, const double* b, int64_t n);
 int dot_owned(iemic_ctx* c, const double* a, const double* b, double* out);
 int idrs(iemic_ctx* c, const double* b, double* x, const iemic_krylov* opt, iemic_solve_info* info);
@@ -710,6 +725,12 @@ int eigs_residual(iemic_ctx* c, double lam_re, double lam_im, double* xr, double
 /* prec.hip */
 int prec_compute(iemic_ctx* c, const iemic_krylov* opt);
 int prec_apply(iemic_ctx* c, const double* r, double* z);
+/* the solvers' stagnation safeguard: the block GS's correction passes take minimal-residual steps
+ * from now on; 0: nothing to switch */
+int prec_safeguard(iemic_ctx* c);
+/* the block GS: set-up (gs_setup.hip) and apply (prec_gs.hip) */
+int gs_compute(iemic_ctx* c, const iemic_krylov* opt);
+int gs_apply(iemic_ctx* c, const double* r, double* z);
 /* the block GS apply from a compressed input (6 rows per ActiveSet::act cell, zero land rows) */
 /* staged: rc is already in the block GS's planar right-hand side (k_dcgs_update) */
 int gs_apply_c(iemic_ctx* c, const double* rc, double* z, bool staged = false);

@@ -1,7 +1,8 @@
 /*
  * gs_internal.h -- what the units of the block Gauss-Seidel preconditioner share
- * (prec_gs.hip, ts_mg.hip, ts_mg_setup.hip, active_set.hip): the Jacobian's slot indices, the subdomain
- * layout seen by their kernels, and the launch helpers.  Included by nothing else.
+ * (prec_gs.hip, gs_setup.hip, gs_dyn.hip, ts_sweeps.hip, ts_mg.hip, ts_mg_setup.hip, active_set.hip):
+ * the Jacobian's slot indices, the subdomain layout seen by their kernels, the launch helpers
+ * and the entries they call in each other.  Included by nothing else.
  */
 #ifndef IEMIC_GS_INTERNAL_H
 #define IEMIC_GS_INTERNAL_H
@@ -25,6 +26,9 @@ constexpr int S_PW0 = 62, S_PWM = 63;               /* P row: W(k), W(k-1)      
 constexpr int S_TT0 = 64, S_TS0 = 81;               /* T row: T self, S self            */
 constexpr int S_SS0 = 84, S_ST0 = 101;              /* S row: S self, T self            */
 constexpr int GSL = 10;                             /* gslot doubles per cell           */
+constexpr int RC_NE = 18;                           /* rcol coefficients per level (gs_dyn.hip) */
+constexpr int MR_NB = 256;                          /* blocks of the minimal-residual dots */
+constexpr int TS_NC = 16;                           /* compact T/S couplings per cell (tsoff) */
 
 /* subdomain layout seen by the kernels (stencil.h ext layout, Decomp2D): n, m global;
  * owned columns [ib0, ib0 + nx), rows from jb0; per-cell arrays are indexed by ext cell,
@@ -66,7 +70,7 @@ __device__ __forceinline__ SubLay sub_of(const Lay& L)
     lc_ijk(L, lc, i, j, k);                                                              \
     (void)i; (void)j; (void)k; (void)ncell
 /* wrap / reject a horizontal neighbour; returns false when outside the domain */
-__device__ __forceinline__ bool hnb(int& i, int& j, int n, int m, int periodic)
+__host__ __device__ __forceinline__ bool hnb(int& i, int& j, int n, int m, int periodic)
 {
     if (j < 0 || j >= m) return false;
     if (i < 0 || i >= n) {
@@ -112,8 +116,6 @@ static Lay lay_of(const Sub& S)
     L.nloc = S.nloc; L.own0 = S.own0; L.ps = S.next;
     return L;
 }
-/* blocks launched for nwg workgroups dealt to the 8 XCDs in contiguous runs (xcd_block) */
-static inline unsigned xcd_grid(int64_t nwg) { return 8u * (unsigned)((nwg + 7) / 8); }
 static unsigned blocks_for(int64_t n) { return (unsigned)((n + 255) / 256); }
 
 /* lanes per z-line (one per level, a power of two >= l; the smoother needs l <= 64) */
@@ -130,6 +132,21 @@ static inline void with_lanes(int P, F&& f)
     }
 }
 #define LANES_OF(p) (decltype(p)::value)
+
+/* the entries the units call in each other: not among the library's dynamic symbols */
+#pragma GCC visibility push(hidden)
+/* gs_dyn.hip: one dynamics pass, z(U/V/W/P) from rr (both component-planar) */
+int dyn_solve(iemic_ctx* c, const double* rr, double* z, double* zo = nullptr, double omega = 0.0,
+              double* zaos = nullptr, bool rr_halo = false, bool schur = true);
+/* does pass it of BlockGS::dyn_iters solve the Schur system (BlockGS::schur_passes)? */
+bool gs_pass_schur(const BlockGS& gs, int it);
+/* the minimal-residual step from BlockGS::dres and dq: zP += w zc, (upd) dres += w dq */
+int dyn_mr_step(iemic_ctx* c, bool upd, double* zaos);
+/* ts_sweeps.hip: its buffers, its colour pack (set-up), and the T/S solve by plain sweeps */
+int ts_sweeps_reserve(iemic_ctx* c);
+void ts_sweeps_pack(iemic_ctx* c);
+int ts_sweeps_solve(iemic_ctx* c, double* z);
+#pragma GCC visibility pop
 
 }  // namespace iemic
 

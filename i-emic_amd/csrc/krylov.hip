@@ -583,8 +583,6 @@ double ms_since(std::chrono::steady_clock::time_point t0)
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
-int prec_safeguard(iemic_ctx* c);
-
 /* a restart cycle of at least STAG_MIN steps that cut the true residual by less than
  * 1 / STAG_RATIO counts as stagnation (a converging cycle at the 2-degree bench state cuts it
  * by ~1e-3, one at the 1-degree continuation tolerance by ~30) */

@@ -6,14 +6,11 @@
  *
  *   prec = 1  cell block-Jacobi: exact 6x6 inverse of every cell's diagonal block.
  *
- * (The block Gauss-Seidel variant after de Niet & Wubs is in prec_gs.hip.)
+ * (The block Gauss-Seidel variant after de Niet & Wubs is in prec_gs.hip and gs_setup.hip.)
  */
 #include "common.h"
 
 namespace iemic {
-
-int gs_compute(iemic_ctx* c, const iemic_krylov* opt);
-int gs_apply(iemic_ctx* c, const double* r, double* z);
 
 /* in-register Gauss-Jordan with partial pivoting of a 6x6 block */
 __device__ __forceinline__ bool inv6(double a[6][6], double inv[6][6])

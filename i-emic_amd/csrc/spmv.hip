@@ -255,7 +255,7 @@ __global__ void __launch_bounds__(256) k_spmv7c(SubLay X, const double* __restri
     }
 }
 
-/* Dynamics defect of the block GS (prec_gs.hip): d = rr - A z on the active U/V/W/P rows,
+/* Dynamics defect of the block GS (prec_gs.hip's correction passes around gs_dyn.hip): d = rr - A z on the active U/V/W/P rows,
  * 0 on the others.  z is the pass iterate, 0 on the identity rows (whose couplings are in
  * rr, the block right-hand side) and on T/S, so rr - A z equals rr_D - A_DD z_D of the
  * block iteration.  One workgroup per 64 cells; the 64 slots of the four rows are split
@@ -383,7 +383,7 @@ int spmv_dyn_defect(iemic_ctx* c, const double* z, const double* r, const uint8_
     const int64_t row = (int64_t)c->l * c->sub.nx;
     const bool hv = halo && gs.act.dvh.p;
     const int nhb = hv ? (int)((2 * row + 63) / 64) : 0;
-    const unsigned grid = 8u * (unsigned)((nblk + nhb + 7) / 8);
+    const unsigned grid = xcd_grid(nblk + nhb);
     hipLaunchKernelGGL(k_spmv_dyn, dim3(grid), dim3(256), 0, c->stream, sub_lay(c->sub), gs.act.vp, z, r, knP, d,
                        c->sub.nloc, nblk, (int64_t)c->sub.next, hv ? gs.act.dvh.p : nullptr, nhb,
                        hv && c->sub.nb[2] >= 0 ? 1 : 0, hv && c->sub.nb[3] >= 0 ? 1 : 0,
@@ -406,7 +406,7 @@ int spmv_kernel(iemic_ctx* c, const double* x, double* y)
     }
     const int tpr = (c->sub.nx + SP7_T - 1) / SP7_T;
     const int ntile = (int)(c->sub.nloc / c->sub.nx) * tpr;
-    const unsigned grid = 8u * (unsigned)((ntile + 7) / 8);
+    const unsigned grid = xcd_grid(ntile);
     hipLaunchKernelGGL(k_spmv7, dim3(grid), dim3(256), 0, s, sub_lay(c->sub), c->d_val.p, x, y, (int)c->sub.nloc, ntile,
                        tpr);
     return spmv_intcond(c, x, c->rowintcon >= 0 ? y + c->rowintcon : nullptr);
@@ -445,7 +445,7 @@ int spmv_kernel_c(iemic_ctx* c, const double* x, double* yc, hipEvent_t ev0, hip
     }
     hipStream_t s = c->stream;
     const int tpr = (c->sub.nx + SP7_T - 1) / SP7_T;
-    const unsigned grid = 8u * (unsigned)((gs.act.natile + 7) / 8);
+    const unsigned grid = xcd_grid(gs.act.natile);
     if (gs.act.natile > 0)
         hipExtLaunchKernelGGL(k_spmv7c, dim3(grid), dim3(256), 0, s, ev0, ev1, 0, sub_lay(c->sub),
                               (const double*)gs.act.spc.p, x, yc, (const int4*)gs.act.atl.p, gs.act.natile, tpr);

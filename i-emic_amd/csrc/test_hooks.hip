@@ -446,11 +446,6 @@ extern "C" int iemic_test_eig_residual(iemic_ctx* c, int64_t N, const double* ar
                               mu_r, mu_i, N, out2);
 }
 
-namespace iemic {
-/* spmv.hip; prec_gs.hip, its caller, declares it for itself */
-int spmv_dyn_defect(iemic_ctx* c, const double* z, const double* r, const uint8_t* knP, double* d, bool halo);
-}  // namespace iemic
-
 extern "C" int iemic_test_active_set(iemic_ctx* c, int64_t* counts, int* act, int* atl)
 {
     if (!c || !counts) return bad("null argument");

@@ -1,6 +1,6 @@
 /*
  * ts_mg.hip -- T/S aggregation multigrid of the block Gauss-Seidel preconditioner
- * (prec_gs.hip, step 6 with ts_mg > 0).
+ * (prec_gs.hip's overview, step 6 with ts_mg > 0).
  *
  * The T/S block is an advection-diffusion operator whose smooth error modes Gauss-Seidel
  * sweeps barely touch.  Its coarse spaces aggregate 2x2 horizontal neighbours over the

@@ -465,7 +465,7 @@ def fgmres(rowptr, col, val, b, prec=None, tol=1e-8, m=500, maxit=500):
 
 
 # ------------------------------------------------------------------------------------
-# block Gauss-Seidel preconditioner (prec_oracle.c) -- CPU twin of prec_gs.hip and ts_mg*.hip
+# block Gauss-Seidel preconditioner (prec_oracle.c) -- CPU twin of prec_gs.hip, gs_dyn.hip, ts_sweeps.hip and ts_mg*.hip
 
 def _load_gs():
     lib = _load_krylov()

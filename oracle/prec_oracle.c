@@ -1,7 +1,7 @@
 /*
  * prec_oracle.c -- TEST INFRASTRUCTURE: CPU restatement of the block Gauss-Seidel
- * preconditioner of i-emic_amd/csrc/prec_gs.hip, written independently on the
- * Epetra-shaped CSR Jacobian (entries looked up by (row, column)), with the 2-D Schur
+ * preconditioner of i-emic_amd/csrc/prec_gs.hip (with gs_setup.hip, gs_dyn.hip and
+ * ts_sweeps.hip), written independently on the Epetra-shaped CSR Jacobian (entries looked up by (row, column)), with the 2-D Schur
  * complement solved by a band LU per application instead of the GPU's dense inverse.
  * It is the checker for the GPU's prec apply and the preconditioner of the CPU
  * baseline's FGMRES.  This is the build's own preconditioner design (the reference's
@@ -34,8 +34,8 @@ typedef struct {
     double* band0;   /* the Schur band before the LU (exported for studies/tests) */
     int* piv;
     double *uvinv, *tsinv, *pw, *rr, *bts, *colv;
-    /* variant of prec_gs.hip's defaults: defect-correction passes on the dynamics block,
-     * T/S by aggregation-multigrid V-cycles (orc_gs_config) */
+    /* variant of gs_setup.hip's defaults (gs_compute): defect-correction passes on the dynamics
+     * block, T/S by aggregation-multigrid V-cycles (orc_gs_config) */
     int dyn_iters, ts_mg;
     int ts_at;                       /* T/S right-hand side after this many dynamics passes */
     double dyn_omega;
@@ -891,7 +891,7 @@ void orc_gs_ts_at(void* h, int ts_at)
  * TRIOS_BlockPreconditioner.C:1479-1611) */
 /* the exact Schur solve in schur_passes of the dynamics passes only: the first k - 1 and the
  * last (k = 1: the first; 0 or >= dyn_iters: all); the others take pbar = 0.  The GPU's
- * BlockGS::schur_passes (iemic_krylov.schur_passes, prec_gs.hip gs_pass_schur) */
+ * BlockGS::schur_passes (iemic_krylov.schur_passes, gs_dyn.hip gs_pass_schur) */
 void orc_gs_schur_passes(void* h, int k) { ((gs_t*)h)->schur_passes = k > 0 ? k : 0; }
 void orc_gs_schur_mask(void* h, int mask) { ((gs_t*)h)->schur_mask = mask; }
 

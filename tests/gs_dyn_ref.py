@@ -1,4 +1,4 @@
-"""What one dynamics pass of the block Gauss-Seidel preconditioner (prec_gs.hip dyn_solve; its
+"""What one dynamics pass of the block Gauss-Seidel preconditioner (gs_dyn.hip dyn_solve; its
 CPU twin oracle/prec_oracle.c dyn_solve) claims to solve, stated as sparse equations: the pass
 is never re-run here, its output is multiplied by a matrix and the rows are checked.  numpy and
 scipy only; float64 matrices, residuals formed in np.longdouble (64-bit mantissa: a product of

@@ -1,4 +1,4 @@
-"""The device's dynamics pass (prec_gs.hip dyn_solve: k_gs_ptil_rcol, the Schur cyclic reduction,
+"""The device's dynamics pass (gs_dyn.hip dyn_solve: k_gs_ptil_rcol, the Schur cyclic reduction,
 k_gs_uvp, k_gs_pw_t) and the defect-correction recurrence around it (gs_apply_impl), through
 Ocean.applyPrecon alone, against the sparse equations of tests/gs_dyn_ref.py: the output is
 multiplied by M_D and every row is checked; nothing is compared with the CPU twin's output.  The
@@ -76,7 +76,7 @@ fmt = R.fmt
 @pytest.mark.parametrize("name", R.FIXTURES)
 def test_single_pass(oracle_lib, Ocean, name, mixing, ts_mg):
     """one pass with the Schur solve; the two T/S settings write the output by different paths
-    (gs_apply_impl zaos_of)"""
+    (prec_gs.hip ApplyPlan::zaos)"""
     c, L0, o, x, ov, ref, ij, pin, rhs = R.problem(oracle_lib, name, mixing)
     params = {"Dyn iterations": 1}
     if ts_mg is not None:

@@ -1,4 +1,4 @@
-"""The block GS set-up with its two factorisations side by side (prec_gs.hip gs_factor: the
+"""The block GS set-up with its two factorisations side by side (gs_setup.hip gs_factor: the
 Schur cyclic reduction on the context's stream, the T/S multigrid set-up on the side stream)
 against the same set-up in serial order (a context created under IEMIC_SERIAL_SETUP=1).
 
