@@ -1,6 +1,6 @@
 /*
  * test_hooks.h -- entry points that drive the dense solvers of the preconditioner on their
- * own (schur_cr.hip, band_lu.hip) for tests/test_gpu_dense.py, and the coupled model's
+ * own (schur_cr.h, band_lu.hip) for tests/test_gpu_dense.py, and the coupled model's
  * preconditioner (coupled.hip) for tests/test_gpu_coupled_krylov.py, and the DCGS2 update pass
  * (krylov.hip) for tests/test_dcgs_fused_coef.py, and the T/S multigrid's plan, levels and
  * fusion switch (iemic_test_ts_mg_plan, iemic_test_ts_mg_level, iemic_test_ts_mg_nofuse;

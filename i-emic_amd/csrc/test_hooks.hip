@@ -4,8 +4,8 @@
  * multigrid's plan and levels read back, the active set read back and the compressed SpMV and
  * the dynamics defect driven on their own (test_hooks.h).
  * No kernels here: every hook stages host data, calls the production entry points of
- * schur_cr.hip / band_lu.hip / coupled.hip / krylov.hip / spmv.hip on the context's stream and copies
- * back.
+ * the cyclic reduction (schur_cr.h: cr_plan.hip, cr_factor.hip, schur_cr.hip, cr_inv.hip) /
+ * band_lu.hip / coupled.hip / krylov.hip / spmv.hip on the context's stream and copies back.
  */
 #include <algorithm>
 #include <cstring>
@@ -140,7 +140,7 @@ extern "C" int iemic_test_cr_inverse(iemic_ctx* c, int m, int count, int s0, int
     if (m < 1 || count < 1 || nsrc < 1 || s0 < 0 || sstep < 1 || (int64_t)s0 + (int64_t)(count - 1) * sstep >= nsrc ||
         count > 4096 || nsrc > 65536)
         return bad("Gauss-Jordan batch out of range");
-    if (m > 192) {                           /* before any allocation: cr_inverse's own refusal */
+    if (m > CR_BLOCK_MAX) {                           /* before any allocation: cr_inverse's own refusal */
         return cr_inverse(c->stream, m, count, nullptr, s0, sstep, nullptr, nullptr);
     }
     const size_t mm = (size_t)m * m;

@@ -448,11 +448,11 @@ static int mg_levels(iemic_ctx* c)
     gs.mg.m[0] = m;
     gs.mg.crd = 0;
     /* one rank: stop at the first level of <= TsMg::CR_CELLS cells that the whole-problem
-     * cyclic reduction takes (blocks of one longitude, 2 m l <= 192 unknowns, >= 2
+     * cyclic reduction takes (blocks of one longitude, 2 m l <= CR_BLOCK_MAX unknowns, >= 2
      * longitudes): an exact coarse solve, one GEMV per V-cycle instead of the last
      * levels' ~9 latency-bound launches */
     auto cr_ok = [&](int nn, int mm) {
-        return c->sub.nranks == 1 && (int64_t)nn * mm * l <= TsMg::CR_CELLS && 2 * mm * l <= 192 && nn >= 2;
+        return c->sub.nranks == 1 && (int64_t)nn * mm * l <= TsMg::CR_CELLS && 2 * mm * l <= CR_BLOCK_MAX && nn >= 2;
     };
     while (q + 1 < TsMg::MAX && (q == 0 || (int64_t)N * M * l > 128) && (N > 1 || M > 1) &&
            !(q > 0 && cr_ok(n, m))) {
@@ -581,8 +581,8 @@ static int mg_coarse_cr(iemic_ctx* c, int qc, int64_t ncl, int N)
     return 0;
 }
 
-/* coarsest level of at most 192 unknowns, one rank: its dense operator assembled and
- * inverted on the device (Gauss-Jordan with pivoting in one workgroup, schur_cr.hip) */
+/* coarsest level of at most CR_BLOCK_MAX unknowns, one rank: its dense operator assembled and
+ * inverted on the device (Gauss-Jordan with pivoting in one workgroup, cr_inv.hip) */
 static int mg_coarse_dev(iemic_ctx* c, int qc, int64_t ncl, int N)
 {
     BlockGS& gs = c->gs;
@@ -703,7 +703,7 @@ int ts_mg_setup(iemic_ctx* c, int sweeps)
     const int qc = gs.mg.nlev - 1;
     const int64_t ncl = (int64_t)gs.mg.n[qc] * gs.mg.m[qc] * c->l;
     const int N = (int)(2 * ncl);
-    gs.mg.ckind = gs.mg.crd ? 1 : (N <= 192 && c->sub.nranks <= 1) ? 0 : 2;
+    gs.mg.ckind = gs.mg.crd ? 1 : (N <= CR_BLOCK_MAX && c->sub.nranks <= 1) ? 0 : 2;
     if (gs.mg.ckind == 1) return mg_coarse_cr(c, qc, ncl, N);
     if (gs.mg.ckind == 0) return mg_coarse_dev(c, qc, ncl, N);
     return mg_coarse_host(c, qc, ncl, N);

@@ -1,5 +1,6 @@
 """The dense solvers of the preconditioner, each on its own, against high-precision references:
-block cyclic reduction (csrc/schur_cr.hip), its batched Gauss-Jordan inverse (k_cr_inv) and
+block cyclic reduction (csrc/schur_cr.hip with cr_plan.hip and cr_factor.hip), its batched Gauss-Jordan
+inverse (k_cr_inv, csrc/cr_inv.hip) and
 the band LU with explicit inverse (csrc/band_lu.hip), through the test hooks of
 csrc/test_hooks.hip (tests/dense_hooks.py).
 
