@@ -1,6 +1,7 @@
 /*
  * capi_time.hip -- the C ABI's timing probes (what bench.py and the profiling scripts read):
- * the SpMV kernel warm and cold, the preconditioner apply and its parts.
+ * the SpMV kernel warm and cold, the block product of the projected model, the preconditioner
+ * apply and its parts.
  */
 #include <chrono>
 
@@ -31,6 +32,44 @@ extern "C" int iemic_time_spmv(iemic_ctx* c, int nrep, double* ms_per_launch)
     float ms = 0;
     HIP_OK(hipEventElapsedTime(&ms, e0, e1));
     *ms_per_launch = ms / nrep;
+    return 0;
+}
+
+/* mean duration of the block product J V of k columns alone (spmm_kernel: the k_spmm7 launches
+ * and, with SRES = 0, the dense row's multi-dot), HIP events on its stream; the columns are
+ * copies of the state, halo rows filled by the warm-up SpMV */
+extern "C" int iemic_time_spmm(iemic_ctx* c, int k, int nrep, double* ms_per_product)
+{
+    CTX_CHECK(c);
+    if (!c->jac_valid || nrep < 1 || !ms_per_product) return IEMIC_ESTATE;
+    if (k < 1 || k > SPMM_MAX_K) {
+        set_error("iemic_time_spmm: k = " + std::to_string(k) + " is outside 1 .. " + std::to_string(SPMM_MAX_K));
+        return IEMIC_EINVAL;
+    }
+    const size_t NE = (size_t)c->sub.nerows();
+    DevBuf<double> V, W;
+    if (V.alloc(NE * k) || W.alloc(NE * k)) {
+        set_error("iemic_time_spmm: out of device memory");
+        return IEMIC_ENOMEM;
+    }
+    EventPair ev;
+    if (ev.create()) {
+        set_error("hipEventCreate failed");
+        return IEMIC_EDEVICE;
+    }
+    int rc = spmv(c, c->d_x.p, c->d_tmp2.p, c->stream); /* fills the state's halo */
+    if (rc) return rc;
+    for (int b = 0; b < k; b++)
+        HIP_OK(hipMemcpyAsync(V.p + b * NE, c->d_x.p, sizeof(double) * NE, hipMemcpyDeviceToDevice, c->stream));
+    if ((rc = spmm_kernel(c, V.p, (int64_t)NE, k, W.p, (int64_t)NE, c->pj.kbmax))) return rc;   /* warm */
+    HIP_OK(hipEventRecord(ev.a, c->stream));
+    for (int r = 0; r < nrep; r++)
+        if ((rc = spmm_kernel(c, V.p, (int64_t)NE, k, W.p, (int64_t)NE, c->pj.kbmax))) return rc;
+    HIP_OK(hipEventRecord(ev.b, c->stream));
+    DEV_WAIT_EVENT(c, ev.b);
+    float ms = 0;
+    HIP_OK(hipEventElapsedTime(&ms, ev.a, ev.b));
+    *ms_per_product = ms / nrep;
     return 0;
 }
 

@@ -293,6 +293,31 @@ struct Stoch {
     int armed = 0;                   /* theta_rhs adds G (iemic_theta_init_step_noise)     */
 };
 
+/* The projected theta model (projected.hip; ProjectedThetaModel.H's V_, smallState_, oldState_,
+ * oldRhs_, VMV_, VAVmat_ / VAVsolver_ and StochasticProjectedThetaModel.H's G_): the state is
+ * confined to x = V y.  V is fixed for the life of the basis and its halo is exchanged once, when
+ * it is set; the small quantities live on the host, identical on every rank. */
+constexpr int SPMM_MAX_K = 64;       /* most columns of a basis / a block product         */
+constexpr int SPMM_KB = 4;           /* columns per k_spmm7 launch (measured)  */
+constexpr int GRAM_T = 4;            /* k_gram: a workgroup's GRAM_T x GRAM_T result tile  */
+constexpr int GRAM_BLOCKS = 256;     /* its row blocks: the partials of one entry          */
+struct Projected {
+    int k = 0;                       /* columns of V (0: no basis)                        */
+    int init = 0;                    /* a step is initialised                             */
+    int armed = 0;                   /* proj_rhs adds G (iemic_proj_init_step_noise)      */
+    int r_valid = 0;                 /* r is the residual at the current small state      */
+    int kbmax = 0;                   /* test hook only: columns per k_spmm7 launch (0: SPMM_KB) */
+    double dt = 0.0, theta = 1.0;
+    DevBuf<double> V, W;             /* k x nerows each: the basis and J2 V / scratch      */
+    DevBuf<double> xold;             /* the state at the init step (proj_restore)         */
+    DevBuf<double> part, res;        /* k_gram's partials (k^2 GRAM_BLOCKS) and results (k^2) */
+    std::vector<double> y, yn, Fn;   /* small state, V^T x_n, V^T F(x_n)                   */
+    std::vector<double> yold;        /* the small state at the init step (proj_restore)   */
+    std::vector<double> VMV, VAV, LU;/* V^T B V, V^T J2 V (row-major k x k) and its factors */
+    std::vector<int> piv;
+    std::vector<double> G, r;        /* the step's noise V^T (B_f pert ...), the residual  */
+};
+
 /* A shift-invert Arnoldi run (eigs.hip): the basis of (J - sigma B)^-1 B and its work vectors,
  * ext layout, allocated by eigs_begin and freed by eigs_end */
 struct Eigs {
@@ -381,8 +406,10 @@ struct iemic_ctx {
     iemic::Krylov kr;
     iemic::Theta th;
     iemic::Stoch st;
+    int64_t ncalls[2] = {0, 0};      /* krylov_solve and prec_compute calls since creation  */
     int64_t frc_gen = 0;             /* counts compute_forcing: what Stoch::coF was made from */
     iemic::Eigs eg;
+    iemic::Projected pj;
     iemic::Geo geo() const;
     iemic_ctx() = default;
     iemic_ctx(const iemic_ctx&) = delete;
@@ -604,6 +631,8 @@ int theta_init_step(iemic_ctx* c, double dt, double theta);
 int theta_rhs(iemic_ctx* c);
 /* J(state) with -B / dt / theta on the diagonal of the U, V, T and S rows */
 int theta_jacobian(iemic_ctx* c);
+/* the same with the caller's dt and theta, no initialised step needed */
+int theta_jacobian_at(iemic_ctx* c, double dt, double theta);
 /* state -= dx on the owned rows; *absmax: this rank's max |dx| (NaN propagates) */
 int theta_update(iemic_ctx* c, const double* dx, double* absmax);
 int theta_restore(iemic_ctx* c);
@@ -615,6 +644,8 @@ int stoch_export(iemic_ctx* c, int64_t* rows, int* cols, double* vals, int64_t* 
 /* after theta_init_step: coF again if the forcing changed, G = (sqrt(dt) sigma) (coF pert[j]),
  * noise armed (sigma = 0: nothing armed) */
 int stoch_arm(iemic_ctx* c, double sigma, const double* pert);
+/* Stoch::G = (sqrt(dt) sigma) (coF pert[j]) alone; disarms the full model's noise */
+int stoch_noise(iemic_ctx* c, double dt, double sigma, const double* pert);
 /* theta_rhs's residual launch while noise is armed: F_theta + G into Theta::Ft, scaled into Theta::b */
 int stoch_theta_residual(iemic_ctx* c);
 /* eigs.hip: shift-invert Arnoldi for J x = lambda B x on the resident state */
@@ -638,6 +669,26 @@ int eigs_residual_sums(iemic_ctx* c, const double* ar, const double* ai, const d
                        const double* B, double mu_r, double mu_i, int64_t N, double* out2);
 /* the two norms of iemic_eigs_residual for ext vectors xr, xi (their halo rows are updated) */
 int eigs_residual(iemic_ctx* c, double lam_re, double lam_im, double* xr, double* xi, double* out2);
+/* spmv.hip: W(:, b) = J V(:, b), b < k <= SPMM_MAX_K, columns ldv / ldw apart (ext layout, halo rows
+ * current), in blocks of kbmax columns per launch (0: SPMM_KB); column b has spmv_kernel's bits */
+int spmm_kernel(iemic_ctx* c, const double* V, int64_t ldv, int k, double* W, int64_t ldw, int kbmax = 0);
+/* projected.hip: the projected theta model (ProjectedThetaModel.H, StochasticProjectedThetaModel.H) */
+/* G (ka x kb, row-major, host) = V^T diag(d) W over the owned rows, summed over the ranks; V, d, W
+ * point at the first owned row (d null: no weights); deterministic (two stages, no atomics) */
+int proj_gram(iemic_ctx* c, const double* V, int64_t ldv, int ka, const double* d, const double* W, int64_t ldw,
+              int kb, double* G);
+/* device buffers for a basis of k columns (Projected::V, W, part, res), the small vectors sized */
+int proj_alloc(iemic_ctx* c, int k);
+int proj_set_basis(iemic_ctx* c, const double* V, int k);
+int proj_clear(iemic_ctx* c);
+int proj_restrict_state(iemic_ctx* c, double* y);
+int proj_set_state(iemic_ctx* c, const double* y);
+int proj_init_step(iemic_ctx* c, double dt, double theta);
+int proj_arm(iemic_ctx* c, double sigma, const double* pert);
+int proj_rhs(iemic_ctx* c, double* r);
+int proj_solve(iemic_ctx* c, const double* r, double* dy);
+int proj_newton_step(iemic_ctx* c, iemic_proj_info* info);
+int proj_restore(iemic_ctx* c);
 /* prec.hip */
 int prec_compute(iemic_ctx* c, const iemic_krylov* opt);
 int prec_apply(iemic_ctx* c, const double* r, double* z);

@@ -916,6 +916,7 @@ int fgmres(iemic_ctx* c, const double* b, double* x, const iemic_krylov* opt, ie
 namespace iemic {
 int krylov_solve(iemic_ctx* c, const double* b, double* x, const iemic_krylov* opt, iemic_solve_info* info)
 {
+    c->ncalls[0]++;
     if (opt->method == 1) return idrs(c, b, x, opt, info);
     if (opt->method != 0) {
         set_error("krylov: unknown method");

@@ -1,7 +1,8 @@
 /*
  * newton.hip -- the C ABI's solve side: the operator (F, J, SpMV), the preconditioner and the
  * linear solves, the Newton iteration, and the entry points of the theta stepper (theta.hip), of
- * its stochastic model (stochastic.hip) and of the linear stability analysis (eigs.hip).
+ * its stochastic model (stochastic.hip), of the projected theta model (projected.hip) and of the
+ * linear stability analysis (eigs.hip).
  *
  * One iteration of transient/Newton.H:92-99 is written once, newton_iterate, over the two
  * models that run it: the steady model (F(x) = 0, iemic_newton_step) and the theta model of a
@@ -319,6 +320,116 @@ extern "C" int iemic_theta_init_step_noise(iemic_ctx* c, double dt, double theta
         }
     const int rc = theta_init_step(c, dt, theta);
     return rc ? rc : stoch_arm(c, sigma, pert);
+}
+
+/* ---- the projected theta model (projected.hip) -------------------------------------------- */
+/* ProjectedThetaModel's constructor (ProjectedThetaModel.H:38-65): the space V */
+extern "C" int iemic_proj_set_basis(iemic_ctx* c, const double* V, int k)
+{
+    CTX_CHECK(c);
+    return proj_set_basis(c, V, k);
+}
+
+extern "C" int iemic_proj_clear(iemic_ctx* c)
+{
+    CTX_CHECK(c);
+    DEV_SYNC(c);
+    return proj_clear(c);
+}
+
+/* ProjectedThetaModel::restrict (ProjectedThetaModel.H:196-206) of the state */
+extern "C" int iemic_proj_restrict_state(iemic_ctx* c, double* y)
+{
+    CTX_CHECK(c);
+    if (!y) return IEMIC_EINVAL;
+    return proj_restrict_state(c, y);
+}
+
+/* ProjectedThetaModel::setState (ProjectedThetaModel.H:114-118) */
+extern "C" int iemic_proj_set_state(iemic_ctx* c, const double* y)
+{
+    CTX_CHECK(c);
+    if (!y) return IEMIC_EINVAL;
+    return proj_set_state(c, y);
+}
+
+/* ProjectedThetaModel::initStep (ProjectedThetaModel.H:70-112) */
+extern "C" int iemic_proj_init_step(iemic_ctx* c, double dt, double theta)
+{
+    CTX_CHECK(c);
+    return proj_init_step(c, dt, theta);
+}
+
+/* StochasticProjectedThetaModel::initStep (StochasticProjectedThetaModel.H:71-92) with the
+ * caller's normals: iemic_theta_init_step_noise's checks */
+extern "C" int iemic_proj_init_step_noise(iemic_ctx* c, double dt, double theta, double sigma, const double* pert)
+{
+    CTX_CHECK(c);
+    if (!pert) {
+        set_error("iemic_proj_init_step_noise: pert is NULL (m standard normals, one per latitude)");
+        return IEMIC_EINVAL;
+    }
+    if (!std::isfinite(sigma) || sigma < 0.0) {
+        set_error("iemic_proj_init_step_noise: sigma must be finite and >= 0");
+        return IEMIC_EINVAL;
+    }
+    for (int j = 0; j < c->m; j++)
+        if (!std::isfinite(pert[j])) {
+            set_error("iemic_proj_init_step_noise: pert[" + std::to_string(j) + "] is not finite");
+            return IEMIC_EINVAL;
+        }
+    const int rc = proj_init_step(c, dt, theta);
+    return rc ? rc : proj_arm(c, sigma, pert);
+}
+
+/* ProjectedThetaModel::computeRHS (ProjectedThetaModel.H:125-155) */
+extern "C" int iemic_proj_rhs(iemic_ctx* c, double* r)
+{
+    CTX_CHECK(c);
+    return proj_rhs(c, r);
+}
+
+/* ProjectedThetaModel::solve (ProjectedThetaModel.H:163-193) */
+extern "C" int iemic_proj_solve(iemic_ctx* c, const double* r, double* dy)
+{
+    CTX_CHECK(c);
+    if (!r || !dy) return IEMIC_EINVAL;
+    return proj_solve(c, r, dy);
+}
+
+/* one iteration of Newton.H:94-99 on the small state */
+extern "C" int iemic_proj_newton_step(iemic_ctx* c, iemic_proj_info* info)
+{
+    CTX_CHECK(c);
+    return proj_newton_step(c, info);
+}
+
+/* AdaptiveTransient.H:107 after a failed Newton run */
+extern "C" int iemic_proj_restore(iemic_ctx* c)
+{
+    CTX_CHECK(c);
+    return proj_restore(c);
+}
+
+/* the model's small vectors and matrices (smallState_, oldState_, oldRhs_, rhs_, G_, VMV_, VAVmat_) */
+extern "C" int iemic_proj_get(iemic_ctx* c, const char* what, double* out)
+{
+    CTX_CHECK(c);
+    if (!what || !out) return IEMIC_EINVAL;
+    const Projected& p = c->pj;
+    if (p.k < 1) {
+        set_error("iemic_proj_get: no basis set (iemic_proj_set_basis)");
+        return IEMIC_ESTATE;
+    }
+    const std::string w(what);
+    const std::vector<double>* v = w == "y" ? &p.y : w == "y_n" ? &p.yn : w == "F_n" ? &p.Fn : w == "r" ? &p.r
+                                 : w == "G" ? &p.G : w == "VMV" ? &p.VMV : w == "VAV" ? &p.VAV : nullptr;
+    if (!v) {
+        set_error("iemic_proj_get: unknown quantity '" + w + "' (y, y_n, F_n, r, G, VMV, VAV)");
+        return IEMIC_EINVAL;
+    }
+    std::copy(v->begin(), v->end(), out);
+    return 0;
 }
 
 /* ---- linear stability analysis (eigs.hip): the JDQZInterface seam ------------------------ */

@@ -264,6 +264,78 @@ class Ocean {
         preProcess();
     }
 
+    /* ---- the projected theta model: what ProjectedThetaModel<Ocean> and
+     * StochasticProjectedThetaModel<Ocean> lay over the model (the state confined to x = V y; the
+     * k x k Newton system is factored on the host, no preconditioner, no Krylov solver) -------- */
+    /* the constructor's V (ProjectedThetaModel.H:38-65): k columns of nrows() doubles, column-major,
+     * 1 <= k <= IEMIC_PROJ_MAX_K, not necessarily orthonormal */
+    void projSetBasis(const std::vector<double>& V, int k)
+    {
+        if (k < 1 || V.size() != (size_t)k * N_)
+            throw std::runtime_error("projSetBasis: V has " + std::to_string(V.size()) + " entries, k x nrows = " +
+                                     std::to_string((size_t)(k < 0 ? 0 : k) * N_));
+        check(iemic_proj_set_basis(ctx_, V.data(), k), "projSetBasis");
+        k_ = (size_t)k;
+    }
+    void projClear()
+    {
+        check(iemic_proj_clear(ctx_), "projClear");
+        k_ = 0;
+    }
+    /* restrict (ProjectedThetaModel.H:196-206) of the state */
+    std::vector<double> projRestrictState()
+    {
+        std::vector<double> y(k_ ? k_ : 1);
+        check(iemic_proj_restrict_state(ctx_, y.data()), "projRestrictState");
+        return y;
+    }
+    /* setState (ProjectedThetaModel.H:114-118): state = V y */
+    void projSetState(const std::vector<double>& y)
+    {
+        if (k_ && y.size() != k_) throw std::runtime_error("projSetState: y has " + std::to_string(y.size()) + " entries");
+        check(iemic_proj_set_state(ctx_, y.data()), "projSetState");
+    }
+    /* initStep (ProjectedThetaModel.H:70-112); with noise StochasticProjectedThetaModel.H:71-92 */
+    void projInitStep(double dt, double theta) { check(iemic_proj_init_step(ctx_, dt, theta), "projInitStep"); }
+    void projStochasticInitStep(double dt, double theta, double sigma, const std::vector<double>& pert)
+    {
+        if (pert.size() != m_)
+            throw std::runtime_error("projStochasticInitStep: pert has " + std::to_string(pert.size()) +
+                                     " entries, the grid has " + std::to_string(m_) + " latitudes");
+        check(iemic_proj_init_step_noise(ctx_, dt, theta, sigma, pert.data()), "projStochasticInitStep");
+    }
+    /* computeRHS (ProjectedThetaModel.H:125-155) and solve (:163-193) */
+    std::vector<double> projRHS()
+    {
+        std::vector<double> r(k_ ? k_ : 1);
+        check(iemic_proj_rhs(ctx_, r.data()), "projRHS");
+        return r;
+    }
+    std::vector<double> projSolve(const std::vector<double>& r)
+    {
+        std::vector<double> dy(k_ ? k_ : 1);
+        if (r.size() != dy.size()) throw std::runtime_error("projSolve: r has " + std::to_string(r.size()) + " entries");
+        check(iemic_proj_solve(ctx_, r.data(), dy.data()), "projSolve");
+        return dy;
+    }
+    /* one iteration of Newton.H:94-99 on the small state */
+    iemic_proj_info projNewtonStep()
+    {
+        iemic_proj_info info{};
+        check(iemic_proj_newton_step(ctx_, &info), "projNewtonStep");
+        return info;
+    }
+    /* the state and the small state as at the init step */
+    void projRestore() { check(iemic_proj_restore(ctx_), "projRestore"); }
+    /* "y", "y_n", "F_n", "r", "G" (k) or "VMV", "VAV" (k x k, row-major) */
+    std::vector<double> projGet(const std::string& what)
+    {
+        const size_t k = k_ ? k_ : 1;
+        std::vector<double> out(what == "VMV" || what == "VAV" ? k * k : k);
+        check(iemic_proj_get(ctx_, what.c_str(), out.data()), "projGet");
+        return out;
+    }
+
     /* ---- linear stability analysis: the calls a JDQZInterface-shaped eigen-solver makes
      * (src/utils/JDQZInterface.H); the Hessenberg eigen-decomposition is the caller's
      * (INTEGRATION.md shows it with LAPACKE_dhseqr / dtrevc) ------------------------- */
@@ -306,7 +378,7 @@ class Ocean {
 
   private:
     iemic_ctx* ctx_ = nullptr;
-    size_t N_ = 0, nm_ = 0, m_ = 0;
+    size_t N_ = 0, nm_ = 0, m_ = 0, k_ = 0;   /* k_: columns of the projected model's basis */
     std::shared_ptr<Vector> state_, rhs_, sol_;
     iemic_krylov krylov_{};
     iemic_solve_info lastSolve_{};

@@ -103,6 +103,7 @@ __global__ void __launch_bounds__(256) k_bj_apply(const double* __restrict__ din
 
 int prec_compute(iemic_ctx* c, const iemic_krylov* opt)
 {
+    c->ncalls[1]++;
     if (!c->jac_valid) {
         set_error("prec_compute: no Jacobian assembled");
         return IEMIC_ESTATE;

@@ -143,6 +143,115 @@ __global__ void __launch_bounds__(256) k_spmv7(SubLay X, const double* __restric
     }
 }
 
+/* k_spmm7<KB>: W(:, b) = J V(:, b) for KB columns per launch (the projected theta model's J2 V,
+ * projected.hip), on the uncompressed slot-major Jacobian.  k_spmv7's tiling: a lane loads its 26
+ * coefficients once and uses them against KB staged neighbourhoods, so the coefficient stream is
+ * read once per KB columns instead of once per column (104 * 8 / KB + 96 bytes per cell and
+ * column).  Column b is at x + b ldx / y + b ldy, ext layout, halo current.
+ * LDS: KB images of 6 * 66 * 6 doubles (19,008 B each); the waves' row partials go into the
+ * start of each column's image once every wave has read it, so KB = 4 takes 76,032 B and two
+ * workgroups stay resident on a CU's 160 KiB.
+ * Every column is formed by sp7_compute from the same v and the same image layout and combined
+ * by the same sums as in k_spmv7: column b of W has the bits of k_spmv7 on column b. */
+template <int KB>
+__global__ void __launch_bounds__(256) k_spmm7(SubLay X, const double* __restrict__ val,
+                                               const double* __restrict__ x, int64_t ldx,
+                                               double* __restrict__ y, int64_t ldy, int nloc, int ntile, int tpr)
+{
+    constexpr int PR = (SP7_T + 2) * NUN, IMG = 6 * PR;
+    constexpr int SPT = (IMG + 255) / 256;
+    static_assert(4 * 3 * SP7_T <= IMG, "the row partials of a column fit in its image");
+    __shared__ double xs[KB * IMG];
+    const int l = X.l, nx = X.nx;
+    const int per = (ntile + 7) >> 3;
+    const int tile = (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);
+    if (tile >= ntile) return;
+    const int row = tile / tpr, i0 = (tile - row * tpr) * SP7_T;
+    const int k = row % l, jl = row / l, j = X.jb0 + jl;
+    const int nc = min(SP7_T, nx - i0);
+    const int lc0 = row * nx + i0;
+    const int t = threadIdx.x, c = t & 63;
+    const int g = __builtin_amdgcn_readfirstlane(t >> 6);   /* wave-uniform: scalar branches */
+    const bool act = c < nc;
+    const int64_t lc = lc0 + c;
+    double acc[KB][3];
+#pragma unroll
+    for (int b = 0; b < KB; b++) acc[b][0] = acc[b][1] = acc[b][2] = 0.0;
+    double v[26];
+    if (g == 0) sp7_load<0, 26>(val, nloc, lc, act, v);
+    else if (g == 1) sp7_load<26, 52>(val, nloc, lc, act, v);
+    else if (g == 2) sp7_load<52, 78>(val, nloc, lc, act, v);
+    else sp7_load<78, 104>(val, nloc, lc, act, v);
+    /* stage the KB neighbourhoods: k_spmv7's image, the source offsets computed once */
+    {
+        const int jm = j > 0 ? j - 1 : j, jp = j < X.m - 1 ? j + 1 : j;
+        const int km = k > 0 ? k - 1 : k, kp = k < l - 1 ? k + 1 : k;
+        const int rj[6] = {jm, j, jp, j, j, jp}, rk[6] = {k, k, k, km, kp, km};
+        const int lim = (nc + 2) * NUN;
+        int64_t src[SPT];
+        int xo[SPT];
+#pragma unroll
+        for (int u = 0; u < SPT; u++) {
+            const int e = t + 256 * u;
+            const int q = e / PR, w = e - q * PR;
+            xo[u] = -1;
+            src[u] = 0;
+            if (e < IMG && w < lim) {
+                const int p = w / NUN, var = w - p * NUN;
+                const int64_t r = (int64_t)(rj[q] - X.jb0 + HALO) * l + rk[q];
+                const int64_t cell = (p == 0 || p == nc + 1)
+                                         ? xnb_cell(r, i0 + p - 1, X.n, X.ib0, nx, X.hx, X.periodic, X.xb)
+                                         : r * nx + i0 + p - 1;
+                xo[u] = e;
+                src[u] = NUN * cell + var;
+            }
+        }
+        double xv[KB][SPT];
+#pragma unroll
+        for (int b = 0; b < KB; b++)
+#pragma unroll
+            for (int u = 0; u < SPT; u++)
+                if (xo[u] >= 0) xv[b][u] = x[(int64_t)b * ldx + src[u]];
+#pragma unroll
+        for (int b = 0; b < KB; b++)
+#pragma unroll
+            for (int u = 0; u < SPT; u++)
+                if (xo[u] >= 0) xs[b * IMG + xo[u]] = xv[b][u];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int b = 0; b < KB; b++) {
+        if (g == 0) sp7_compute<0, 26>(v, xs + b * IMG, c, acc[b]);
+        else if (g == 1) sp7_compute<26, 52>(v, xs + b * IMG, c, acc[b]);
+        else if (g == 2) sp7_compute<52, 78>(v, xs + b * IMG, c, acc[b]);
+        else sp7_compute<78, 104>(v, xs + b * IMG, c, acc[b]);
+    }
+    __syncthreads();                    /* every image is read: its start now holds red[4][3][64] */
+#pragma unroll
+    for (int b = 0; b < KB; b++)
+#pragma unroll
+        for (int q = 0; q < 3; q++) xs[b * IMG + (g * 3 + q) * SP7_T + c] = acc[b][q];
+    __syncthreads();
+    /* rows of the groups as in k_spmv7: g0 {U,V} g1 {V,W} g2 {W,P,T} g3 {T,S} */
+#pragma unroll
+    for (int b = 0; b < KB; b++) {
+        const double* red = xs + b * IMG;
+        for (int o = t; o < nc * NUN; o += 256) {
+            const int cc = o / NUN, R = o - cc * NUN;
+            double vv;
+            switch (R) {
+            case 0: vv = red[(0 * 3 + 0) * SP7_T + cc]; break;
+            case 1: vv = red[(0 * 3 + 1) * SP7_T + cc] + red[(1 * 3 + 0) * SP7_T + cc]; break;
+            case 2: vv = red[(1 * 3 + 1) * SP7_T + cc] + red[(2 * 3 + 0) * SP7_T + cc]; break;
+            case 3: vv = red[(2 * 3 + 1) * SP7_T + cc]; break;
+            case 4: vv = red[(2 * 3 + 2) * SP7_T + cc] + red[(3 * 3 + 0) * SP7_T + cc]; break;
+            default: vv = red[(3 * 3 + 1) * SP7_T + cc]; break;
+            }
+            y[(int64_t)b * ldy + NUN * ((int64_t)HALO * l * nx + lc0) + o] = vv;
+        }
+    }
+}
+
 /* k_spmv7c: the in-solve SpMV of FGMRES's compressed basis (round 6).  k_spmv7 reads the
  * slot-major Jacobian, whose 128-byte coefficient lines hold 16 cells: the lines of mixed land /
  * water runs are fetched whole (at 2 degrees 128.9 MB of coefficient lines for 100.7 MB of
@@ -458,6 +567,65 @@ int spmv_kernel_c(iemic_ctx* c, const double* x, double* yc, hipEvent_t ev0, hip
         yr = yc + c->gs.act.ric;
     }
     return spmv_intcond(c, x, yr);
+}
+
+/* W[b ldw + rowintcon] = s res[b], b < k: the dense row's entries of the block product */
+__global__ void k_intcond_put(const double* __restrict__ res, double s, double* __restrict__ w, int64_t ldw, int k)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < k) w[(int64_t)b * ldw] = s * res[b];
+}
+
+template <int KB>
+static void spmm_launch(iemic_ctx* c, const double* V, int64_t ldv, double* W, int64_t ldw, int ntile, int tpr)
+{
+    hipLaunchKernelGGL(k_spmm7<KB>, dim3(xcd_grid(ntile)), dim3(256), 0, c->stream, sub_lay(c->sub), c->d_val.p, V, ldv, W,
+                       ldw, (int)c->sub.nloc, ntile, tpr);
+}
+
+/* W(:, b) = J V(:, b), b < k, on the owned rows: full blocks of kbmax columns (4, 2 or 1; 0: the
+ * default), then the remainder in narrower blocks; the columns' halo rows must be current.
+ * The dense integral-condition row follows spmv_intcond: one multi-dot of the k columns
+ * against d_intc (the partials in d_part), one all-reduce of k values. */
+int spmm_kernel(iemic_ctx* c, const double* V, int64_t ldv, int k, double* W, int64_t ldw, int kbmax)
+{
+    if (!c->jac_valid) {
+        set_error("spmm: no Jacobian assembled");
+        return IEMIC_ESTATE;
+    }
+    if (c->sub.nloc >= INT32_MAX) {
+        set_error("spmm: more than 2^31 cells per rank");
+        return IEMIC_EINVAL;
+    }
+    if (k < 1 || k > SPMM_MAX_K) {
+        set_error("spmm: the number of columns must lie in 1 .. " + std::to_string(SPMM_MAX_K));
+        return IEMIC_EINVAL;
+    }
+    const int kb = kbmax == 1 || kbmax == 2 || kbmax == 4 ? kbmax : SPMM_KB;
+    const int tpr = (c->sub.nx + SP7_T - 1) / SP7_T;
+    const int ntile = (int)(c->sub.nloc / c->sub.nx) * tpr;
+    int b = 0;
+    if (kb == 4)
+        for (; b + 4 <= k; b += 4) spmm_launch<4>(c, V + b * ldv, ldv, W + b * ldw, ldw, ntile, tpr);
+    if (kb >= 2)
+        for (; b + 2 <= k; b += 2) spmm_launch<2>(c, V + b * ldv, ldv, W + b * ldw, ldw, ntile, tpr);
+    for (; b < k; b++) spmm_launch<1>(c, V + b * ldv, ldv, W + b * ldw, ldw, ntile, tpr);
+    HIP_OK(hipGetLastError());
+    if (c->su.rowintcon_ref >= 0) {
+        const Owned w = owned(c);
+        double* part = c->d_part.p;
+        double* res = part + (size_t)RED_BLOCKS * k;
+        hipLaunchKernelGGL(k_mdot, dim3(RED_BLOCKS, k), dim3(256), 0, c->stream, V + w.o, ldv, k, c->d_intc.p + w.o, w.n,
+                           part);
+        hipLaunchKernelGGL(k_mdot_final, dim3(k), dim3(256), 0, c->stream, part, RED_BLOCKS, k, res);
+        int rc = allreduce_sum(c, res, k);
+        if (rc) return rc;
+        if (c->rowintcon >= 0)
+            hipLaunchKernelGGL(k_intcond_put, dim3(1), dim3(64), 0, c->stream, res, (double)c->cfg.int_sign,
+                               W + c->rowintcon, ldw, k);
+        HIP_OK(hipGetLastError());
+    }
+    return 0;
 }
 
 int spmv(iemic_ctx* c, double* x, double* y, hipStream_t)

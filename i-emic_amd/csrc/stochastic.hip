@@ -146,18 +146,28 @@ int stoch_export(iemic_ctx* c, int64_t* rows, int* cols, double* vals, int64_t* 
  * for theta_rhs.  sigma = 0 arms nothing: the residual stays k_theta_residual's. */
 int stoch_arm(iemic_ctx* c, double sigma, const double* pert)
 {
+    c->st.armed = 0;
+    if (sigma == 0.0) return 0;
+    const int rc = stoch_noise(c, c->th.dt, sigma, pert);
+    if (rc) return rc;
+    c->st.armed = 1;
+    return 0;
+}
+
+/* Stoch::G of a step of length dt, nothing armed: stoch_arm's field, which the projected model
+ * restricts (projected.hip).  The full model's noise is disarmed: the field is shared. */
+int stoch_noise(iemic_ctx* c, double dt, double sigma, const double* pert)
+{
     Stoch& st = c->st;
     st.armed = 0;
-    if (sigma == 0.0) return 0;
     int rc = stoch_alloc(c);
     if (rc) return rc;
     if (st.gen != c->frc_gen && (rc = stoch_forcing(c))) return rc;
     if ((rc = h2d(c, st.pert.p, pert, sizeof(double) * (size_t)c->m))) return rc;
     const int ns = c->sub.nx * c->sub.mb;
     hipLaunchKernelGGL(k_stoch_noise, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, c->stream, c->geo(),
-                       st.coF.p, st.pert.p, std::sqrt(c->th.dt) * sigma, (int64_t)c->rowintcon, st.G.p, ns);
+                       st.coF.p, st.pert.p, std::sqrt(dt) * sigma, (int64_t)c->rowintcon, st.G.p, ns);
     HIP_OK(hipGetLastError());
-    st.armed = 1;
     return 0;
 }
 

@@ -10,7 +10,10 @@
  * kernels of the stability analysis (eigs.hip) for tests/test_gpu_eigs.py, and the active set with its
  * tile descriptors, the compressed SpMV beside the full one and the dynamics defect
  * (iemic_test_active_set, iemic_test_spmv_c, iemic_test_dyn_defect; active_set.hip, spmv.hip) for
- * tests/test_gpu_spmv_tiles.py.  They are exported from the
+ * tests/test_gpu_spmv_tiles.py, and the projected model's block product and Gram product
+ * (iemic_test_spmm, iemic_test_spmm_kb, iemic_test_gram, iemic_test_gram_cost,
+ * iemic_test_solver_calls; spmv.hip,
+ * projected.hip) for tests/test_gpu_projected.py.  They are exported from the
  * device library but are NOT part of its public ABI (include/iemic.h, IEMIC_ABI_VERSION):
  * tests/dense_hooks.py binds them.  All pointers are host pointers; every hook runs on the
  * context's stream, owns its device buffers and returns the usual IEMIC_* codes.
@@ -147,6 +150,29 @@ int iemic_test_spmv_c(iemic_ctx* ctx, const double* x, double* yc, double* y, in
  * NaN bit patterns (what the kernel does not write comes back as such).  The hook's buffers are
  * its own: none of the preconditioner's work vectors is touched. */
 int iemic_test_dyn_defect(iemic_ctx* ctx, int64_t NE, const double* z, const double* rr, double* d);
+
+/* The block product of the projected model (spmm_kernel, spmv.hip) on k host columns V (each
+ * in the reference order, staged as iemic_spmv stages its x, halo exchange included; collective
+ * on several ranks): W (k columns, reference order) receives this rank's owned rows, from a
+ * device buffer of NaN bit patterns.  kbmax: columns per k_spmm7 launch, 1, 2 or 4 (0: default). */
+int iemic_test_spmm(iemic_ctx* ctx, int k, int kbmax, const double* V, double* W);
+
+/* columns per k_spmm7 launch in iemic_proj_init_step and iemic_time_spmm until changed (0: default) */
+int iemic_test_spmm_kb(iemic_ctx* ctx, int kbmax);
+
+/* G (ka x kb, row-major) = V^T diag(d) W by proj_gram (projected.hip) on host columns in the
+ * reference order (d: one column, or NULL); a basis of at least max(ka, kb) columns must be set
+ * (its work space is used).  Summed over the ranks. */
+int iemic_test_gram(iemic_ctx* ctx, int ka, int kb, const double* V, const double* d, const double* W, double* G);
+
+/* Measurement helper (one rank): GPU milliseconds per k x k Gram product of the set basis and its
+ * scratch, results fetched, nrep each: by proj_gram (ms[0]), by k multi-dot pairs each fetched on
+ * its own (ms[1]) and by the same k launch pairs with one fetch (ms[2]). */
+int iemic_test_gram_cost(iemic_ctx* ctx, int k, int nrep, double* ms);
+
+/* out[0], out[1]: the calls of krylov_solve (FGMRES or IDR(s), from any entry point) and of
+ * prec_compute since the context was created */
+int iemic_test_solver_calls(iemic_ctx* ctx, int64_t* out);
 
 #ifdef __cplusplus
 }

@@ -14,6 +14,7 @@
 #include "common.h"
 #include "coupled_internal.h"
 #include "krylov_internal.h"
+#include "vec_kernels.h"
 #include "test_hooks.h"
 
 using namespace iemic;
@@ -519,4 +520,126 @@ extern "C" int iemic_test_dyn_defect(iemic_ctx* c, int64_t NE, const double* z, 
     if ((rc = spmv_dyn_defect(c, zd.p, rd.p, gs.knP.p, dd.p, false))) return rc;
     HIP_OK(hipGetLastError());
     return d2h(c, d, dd.p, sizeof(double) * NE);
+}
+
+/* columns of host vectors in the reference order -> ext columns ld apart on the device, halo
+ * rows exchanged (collective on several ranks) */
+static int put_columns(iemic_ctx* c, const double* H, int k, double* D, int64_t ld)
+{
+    std::vector<double> e((size_t)ld);
+    for (int b = 0; b < k; b++) {
+        std::fill(e.begin(), e.end(), 0.0);
+        c->su.ref_to_ext(H + (int64_t)b * c->nrows, e.data());
+        int rc = h2d(c, D + (int64_t)b * ld, e.data(), sizeof(double) * (size_t)ld);
+        if (!rc) rc = halo_exchange(c, D + (int64_t)b * ld, HALO);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+extern "C" int iemic_test_spmm(iemic_ctx* c, int k, int kbmax, const double* V, double* W)
+{
+    if (!c || !V || !W) return bad("null argument");
+    if (k < 1 || k > SPMM_MAX_K) return bad("k out of range");
+    if (hipSetDevice(c->device) != hipSuccess) return IEMIC_EDEVICE;
+    StreamGuard guard{c};
+    const int64_t ld = c->sub.nerows();
+    DevBuf<double> vd, wd;
+    if (vd.alloc((size_t)ld * k) || wd.alloc((size_t)ld * k)) return IEMIC_ENOMEM;
+    int rc = put_columns(c, V, k, vd.p, ld);
+    if (rc) return rc;
+    HIP_OK(hipMemsetAsync(wd.p, 0xff, sizeof(double) * (size_t)ld * k, c->stream));
+    if ((rc = spmm_kernel(c, vd.p, ld, k, wd.p, ld, kbmax))) return rc;
+    std::vector<double> e((size_t)ld);
+    for (int b = 0; b < k; b++) {
+        if ((rc = d2h(c, e.data(), wd.p + (int64_t)b * ld, sizeof(double) * (size_t)ld))) return rc;
+        c->su.ext_to_ref(e.data(), W + (int64_t)b * c->nrows);
+    }
+    return 0;
+}
+
+extern "C" int iemic_test_spmm_kb(iemic_ctx* c, int kbmax)
+{
+    if (!c) return bad("null argument");
+    if (kbmax != 0 && kbmax != 1 && kbmax != 2 && kbmax != 4) return bad("kbmax must be 0, 1, 2 or 4");
+    c->pj.kbmax = kbmax;
+    return 0;
+}
+
+extern "C" int iemic_test_gram(iemic_ctx* c, int ka, int kb, const double* V, const double* d, const double* W,
+                               double* G)
+{
+    if (!c || !V || !W || !G) return bad("null argument");
+    if (ka < 1 || kb < 1 || ka > c->pj.k || kb > c->pj.k) return bad("set a basis of at least max(ka, kb) columns first");
+    if (hipSetDevice(c->device) != hipSuccess) return IEMIC_EDEVICE;
+    StreamGuard guard{c};
+    const int64_t ld = c->sub.nerows();
+    DevBuf<double> vd, wd, dd;
+    if (vd.alloc((size_t)ld * ka) || wd.alloc((size_t)ld * kb) || (d && dd.alloc((size_t)ld))) return IEMIC_ENOMEM;
+    int rc = put_columns(c, V, ka, vd.p, ld);
+    if (!rc) rc = put_columns(c, W, kb, wd.p, ld);
+    if (!rc && d) rc = put_columns(c, d, 1, dd.p, ld);
+    if (rc) return rc;
+    const Owned o = owned(c);
+    return proj_gram(c, vd.p + o.o, ld, ka, d ? dd.p + o.o : nullptr, wd.p + o.o, ld, kb, G);
+}
+
+extern "C" int iemic_test_gram_cost(iemic_ctx* c, int k, int nrep, double* ms)
+{
+    if (!c || !ms || nrep < 1) return bad("null argument");
+    if (k < 1 || k > c->pj.k) return bad("set a basis of at least k columns first");
+    if (c->sub.nranks != 1) return bad("a single-rank context is needed");
+    if (hipSetDevice(c->device) != hipSuccess) return IEMIC_EDEVICE;
+    StreamGuard guard{c};
+    const int64_t ld = c->sub.nerows();
+    const Owned o = owned(c);
+    const Projected& p = c->pj;
+    std::vector<double> G((size_t)k * k);
+    EventPair ev;
+    if (ev.create()) return IEMIC_EDEVICE;
+    int rc = proj_gram(c, p.V.p + o.o, ld, k, nullptr, p.W.p + o.o, ld, k, G.data());   /* warm */
+    if (rc) return rc;
+    float t = 0;
+    HIP_OK(hipEventRecord(ev.a, c->stream));
+    for (int r = 0; r < nrep; r++)
+        if ((rc = proj_gram(c, p.V.p + o.o, ld, k, nullptr, p.W.p + o.o, ld, k, G.data()))) return rc;
+    HIP_OK(hipEventRecord(ev.b, c->stream));
+    DEV_WAIT_EVENT(c, ev.b);
+    HIP_OK(hipEventElapsedTime(&t, ev.a, ev.b));
+    ms[0] = t / nrep;
+    /* what it replaces: one multi-dot pair per column of W, its k results fetched */
+    HIP_OK(hipEventRecord(ev.a, c->stream));
+    for (int r = 0; r < nrep; r++)
+        for (int b = 0; b < k; b++)
+            if ((rc = mdot_host(c, p.V.p + o.o, ld, k, p.W.p + (int64_t)b * ld + o.o, G.data() + (size_t)b * k))) return rc;
+    HIP_OK(hipEventRecord(ev.b, c->stream));
+    DEV_WAIT_EVENT(c, ev.b);
+    HIP_OK(hipEventElapsedTime(&t, ev.a, ev.b));
+    ms[1] = t / nrep;
+    /* the same launches with one fetch: k multi-dot pairs into the rows of one result array */
+    DevBuf<double> res;
+    if (res.alloc((size_t)k * k)) return IEMIC_ENOMEM;
+    HIP_OK(hipEventRecord(ev.a, c->stream));
+    for (int r = 0; r < nrep; r++) {
+        for (int b = 0; b < k; b++) {
+            hipLaunchKernelGGL(k_mdot, dim3(RED_BLOCKS, k), dim3(256), 0, c->stream, p.V.p + o.o, ld, k,
+                               p.W.p + (int64_t)b * ld + o.o, o.n, c->d_part.p);
+            hipLaunchKernelGGL(k_mdot_final, dim3(k), dim3(256), 0, c->stream, c->d_part.p, RED_BLOCKS, k,
+                               res.p + (size_t)b * k);
+        }
+        if ((rc = d2h(c, G.data(), res.p, sizeof(double) * k * k))) return rc;
+    }
+    HIP_OK(hipEventRecord(ev.b, c->stream));
+    DEV_WAIT_EVENT(c, ev.b);
+    HIP_OK(hipEventElapsedTime(&t, ev.a, ev.b));
+    ms[2] = t / nrep;
+    return 0;
+}
+
+extern "C" int iemic_test_solver_calls(iemic_ctx* c, int64_t* out)
+{
+    if (!c || !out) return bad("null argument");
+    out[0] = c->ncalls[0];
+    out[1] = c->ncalls[1];
+    return 0;
 }

@@ -141,11 +141,17 @@ int theta_jacobian(iemic_ctx* c)
 {
     int rc = theta_ready(c, "iemic_theta_jacobian");
     if (rc) return rc;
-    if ((rc = halo_exchange(c, c->d_x.p, HALO))) return rc;
+    return theta_jacobian_at(c, c->th.dt, c->th.theta);
+}
+
+/* the same for a step the caller holds (the projected model's, projected.hip) */
+int theta_jacobian_at(iemic_ctx* c, double dt, double theta)
+{
+    int rc = halo_exchange(c, c->d_x.p, HALO);
+    if (rc) return rc;
     if ((rc = assemble_jacobian(c, c->d_x.p))) return rc;
     hipLaunchKernelGGL(k_theta_shift, dim3((unsigned)((c->sub.nloc + 255) / 256), THETA_ROWS), dim3(256), 0,
-                       c->stream, c->d_B.p, c->d_val.p, (int64_t)c->sub.own0, (int64_t)c->sub.nloc, c->th.dt,
-                       c->th.theta);
+                       c->stream, c->d_B.p, c->d_val.p, (int64_t)c->sub.own0, (int64_t)c->sub.nloc, dt, theta);
     HIP_OK(hipGetLastError());
     return 0;
 }

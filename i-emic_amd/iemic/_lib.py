@@ -16,7 +16,7 @@ PKG_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(PKG_DIR, "lib", os.environ.get("IEMIC_LIB", "libiemic_amd.so"))
 
 IEMIC_ENODEV = -19
-ABI_VERSION = 10            # IEMIC_ABI_VERSION of include/iemic.h this binding mirrors
+ABI_VERSION = 11            # IEMIC_ABI_VERSION of include/iemic.h this binding mirrors
 IEMIC_ENOCONV = 1           # iemic_newton_step: applied, but the solve missed its tolerance
 
 
@@ -88,6 +88,14 @@ class ThetaInfo(C.Structure):
     _fields_ = [("norm_f0", C.c_double), ("norm_f1", C.c_double), ("norm_dx", C.c_double),
                 ("solve", SolveInfo), ("t_jac_ms", C.c_double), ("t_rhs_ms", C.c_double),
                 ("t_prec_ms", C.c_double), ("t_solve_ms", C.c_double), ("t_total_ms", C.c_double)]
+
+
+class ProjInfo(C.Structure):
+    """iemic_proj_info: one Newton iteration of the projected theta model."""
+    _fields_ = [("norm_dx", C.c_double), ("norm_f1", C.c_double), ("t_total_ms", C.c_double)]
+
+
+PROJ_MAX_K = 64             # IEMIC_PROJ_MAX_K
 
 
 class EigsInfo(C.Structure):
@@ -183,6 +191,17 @@ def lib():
         "iemic_forcing_compute": (C.c_int, [vp]),
         "iemic_forcing_export": (C.c_int, [vp, P64, PI, PD, P64]),
         "iemic_theta_init_step_noise": (C.c_int, [vp, C.c_double, C.c_double, C.c_double, PD]),
+        "iemic_proj_set_basis": (C.c_int, [vp, PD, C.c_int]),
+        "iemic_proj_clear": (C.c_int, [vp]),
+        "iemic_proj_restrict_state": (C.c_int, [vp, PD]),
+        "iemic_proj_set_state": (C.c_int, [vp, PD]),
+        "iemic_proj_init_step": (C.c_int, [vp, C.c_double, C.c_double]),
+        "iemic_proj_init_step_noise": (C.c_int, [vp, C.c_double, C.c_double, C.c_double, PD]),
+        "iemic_proj_rhs": (C.c_int, [vp, PD]),
+        "iemic_proj_solve": (C.c_int, [vp, PD, PD]),
+        "iemic_proj_newton_step": (C.c_int, [vp, P(ProjInfo)]),
+        "iemic_proj_restore": (C.c_int, [vp]),
+        "iemic_proj_get": (C.c_int, [vp, C.c_char_p, PD]),
         "iemic_shifted_jacobian": (C.c_int, [vp, C.c_double]),
         "iemic_eigs_begin": (C.c_int, [vp, C.c_double, C.c_int, C.c_uint64, P(Krylov)]),
         "iemic_eigs_step": (C.c_int, [vp, P(Krylov), PD, P(EigsInfo)]),
@@ -200,6 +219,7 @@ def lib():
         "iemic_state_vec": (C.c_int, [vp, vp, C.c_int]),
         "iemic_rhs_vec": (C.c_int, [vp, vp]),
         "iemic_time_spmv": (C.c_int, [vp, C.c_int, PD]),
+        "iemic_time_spmm": (C.c_int, [vp, C.c_int, C.c_int, PD]),
         "iemic_time_prec": (C.c_int, [vp, C.c_int, PD, PD]),
         "iemic_time_prec_parts": (C.c_int, [vp, C.c_int, PD]),
         "iemic_time_spmv_cold": (C.c_int, [vp, C.c_int, vp, C.c_int64, PD]),
@@ -271,6 +291,9 @@ EXPORTED = ("iemic_abi_version", "iemic_create", "iemic_create_dist", "iemic_com
             "iemic_solve_dev", "iemic_newton_step", "iemic_theta_init_step", "iemic_theta_rhs",
             "iemic_theta_jacobian", "iemic_theta_restore", "iemic_theta_newton_step",
             "iemic_forcing_compute", "iemic_forcing_export", "iemic_theta_init_step_noise",
+            "iemic_proj_set_basis", "iemic_proj_clear", "iemic_proj_restrict_state", "iemic_proj_set_state",
+            "iemic_proj_init_step", "iemic_proj_init_step_noise", "iemic_proj_rhs", "iemic_proj_solve",
+            "iemic_proj_newton_step", "iemic_proj_restore", "iemic_proj_get", "iemic_time_spmm",
             "iemic_shifted_jacobian", "iemic_eigs_begin", "iemic_eigs_step", "iemic_eigs_ritz",
             "iemic_eigs_restart", "iemic_eigs_residual", "iemic_eigs_end", "iemic_vec_alloc", "iemic_vec_free",
             "iemic_vec_update", "iemic_vec_dot", "iemic_vec_norm_inf", "iemic_vec_from_ref",

@@ -167,6 +167,7 @@ class Ocean:
             sp.update(solver_params)
         self.solver_params = sp
         self._recomp_prec = True
+        self._proj_k = 0                # columns of the projected model's basis (projSetBasis)
         for idx, v in cfg.par_list():
             self.setPar(idx, v)
         self._x = np.zeros(self.N)
@@ -727,6 +728,94 @@ class Ocean:
         check(lib().iemic_theta_init_step_noise(self._h, float(dt), float(theta), float(sigma), ptr(pert)),
               "iemic_theta_init_step_noise")
 
+    # ---- the projected theta model (ProjectedThetaModel<Ocean>; iemic.transient) ----------
+    def projSetBasis(self, V) -> None:
+        """The space V of ProjectedThetaModel (ProjectedThetaModel.H:38-65): an N x k array, 1 <= k
+        <= 64, each column in setState's layout; it need not be orthonormal.  The state is then
+        confined to x = V y and the small state starts as V^T state.  V is copied to the device
+        once (its halo rows exchanged here) and stays fixed until projClear or the next basis."""
+        V = np.asarray(V, dtype=np.float64)
+        if V.ndim != 2 or V.shape[0] != self.N:
+            raise IemicError(f"projSetBasis: V has shape {V.shape}, the model has {self.N} rows")
+        k = V.shape[1]
+        Vc = np.ascontiguousarray(V.T)                 # column-major N x k
+        check(lib().iemic_proj_set_basis(self._h, ptr(Vc), int(k)), "iemic_proj_set_basis")
+        self._proj_k = k
+
+    def projClear(self) -> None:
+        check(lib().iemic_proj_clear(self._h), "iemic_proj_clear")
+        self._proj_k = 0
+
+    def _proj_vec(self, n=None) -> np.ndarray:
+        return np.zeros(max(1, self._proj_k) if n is None else n)
+
+    def projRestrictState(self) -> np.ndarray:
+        """restrict (ProjectedThetaModel.H:196-206): V^T state."""
+        y = self._proj_vec()
+        check(lib().iemic_proj_restrict_state(self._h, ptr(y)), "iemic_proj_restrict_state")
+        return y
+
+    def projSetState(self, y) -> None:
+        """setState (ProjectedThetaModel.H:114-118): state = V y, small state = y."""
+        y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+        if self._proj_k and y.size != self._proj_k:
+            raise IemicError(f"projSetState: y has {y.size} entries, the basis has {self._proj_k} columns")
+        if not self._proj_k:
+            y = np.zeros(1)                            # refused by name below: no basis
+        check(lib().iemic_proj_set_state(self._h, ptr(y)), "iemic_proj_set_state")
+
+    def projInitStep(self, dt: float, theta: float) -> None:
+        """initStep (ProjectedThetaModel.H:70-112): y_n = V^T state (of the large state, not the
+        stored y), F_n = V^T F(state), VMV = V^T B V, J2 = J - B / dt / theta, VAV = V^T J2 V and
+        its LU factors.  theta outside (0, 1] (the reference's theta = 0 branch is left out),
+        dt <= 0 and a singular VAV raise IemicError by name.  Disarms the noise."""
+        check(lib().iemic_proj_init_step(self._h, float(dt), float(theta)), "iemic_proj_init_step")
+
+    def projStochasticInitStep(self, dt: float, theta: float, sigma: float, pert) -> None:
+        """StochasticProjectedThetaModel::initStep (:71-92): projInitStep, then G = V^T of
+        stochasticInitStep's noise field, added to the residual until the next init step.
+        pert and sigma: stochasticInitStep's rules."""
+        pert = np.ascontiguousarray(pert, dtype=np.float64).reshape(-1)
+        if pert.size != self.cfg.m:
+            raise IemicError(f"projStochasticInitStep: pert has {pert.size} entries, the grid has "
+                             f"{self.cfg.m} latitudes")
+        check(lib().iemic_proj_init_step_noise(self._h, float(dt), float(theta), float(sigma), ptr(pert)),
+              "iemic_proj_init_step_noise")
+
+    def projRHS(self) -> np.ndarray:
+        """computeRHS (ProjectedThetaModel.H:125-155):
+        r = dt (1 - theta) F_n + dt theta V^T F(state) + VMV (y_n - y) [+ G]."""
+        r = self._proj_vec()
+        check(lib().iemic_proj_rhs(self._h, ptr(r)), "iemic_proj_rhs")
+        return r
+
+    def projSolve(self, r) -> np.ndarray:
+        """solve (ProjectedThetaModel.H:163-193): VAV dy = r / dt / theta."""
+        r = np.ascontiguousarray(r, dtype=np.float64).reshape(-1)
+        dy = self._proj_vec()
+        if r.size != dy.size:
+            raise IemicError(f"projSolve: r has {r.size} entries, the basis has {dy.size} columns")
+        check(lib().iemic_proj_solve(self._h, ptr(r), ptr(dy)), "iemic_proj_solve")
+        return dy
+
+    def projNewtonStep(self) -> _lib.ProjInfo:
+        """One iteration of Newton.H:94-99 on the small state: dy from the current r, y -= dy,
+        state = V y, F, r; info.norm_dx = ||dy||_inf, info.norm_f1 = ||r||_2."""
+        info = _lib.ProjInfo()
+        check(lib().iemic_proj_newton_step(self._h, C.byref(info)), "iemic_proj_newton_step")
+        return info
+
+    def projRestore(self) -> None:
+        """The state and the small state as they were at the init step (after a failed Newton run)."""
+        check(lib().iemic_proj_restore(self._h), "iemic_proj_restore")
+
+    def projGet(self, what: str) -> np.ndarray:
+        """The model's small quantities: "y", "y_n", "F_n", "r", "G" (k) or "VMV", "VAV" (k x k)."""
+        k = max(1, self._proj_k)
+        out = np.zeros(k * k if what in ("VMV", "VAV") else k)
+        check(lib().iemic_proj_get(self._h, what.encode(), ptr(out)), "iemic_proj_get")
+        return out.reshape(k, k) if what in ("VMV", "VAV") else out
+
     # ---- linear stability analysis (the JDQZInterface seam; iemic.eigs) -----------------
     def shiftedJacobian(self, sigma: float) -> None:
         """J - sigma B at the current state (J is assembled first); exportCSR, applyMatrix,
@@ -789,6 +878,12 @@ class Ocean:
     def time_spmv(self, nrep: int = 20) -> float:
         ms = C.c_double()
         check(lib().iemic_time_spmv(self._h, int(nrep), C.byref(ms)), "iemic_time_spmv")
+        return ms.value
+
+    def time_spmm(self, k: int, nrep: int = 20) -> float:
+        """Mean GPU ms of one block product J V of k columns (iemic_time_spmm)."""
+        ms = C.c_double()
+        check(lib().iemic_time_spmm(self._h, int(k), int(nrep), C.byref(ms)), "iemic_time_spmm")
         return ms.value
 
     def time_prec(self, nrep: int = 20):

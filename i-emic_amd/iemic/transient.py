@@ -22,8 +22,26 @@ Transient.hpp:138-145).
 
 ``StochasticThetaStepper`` is the same loop on ``StochasticThetaModel<Ocean>``
 (StochasticThetaModel.H): every step starts with ``stochasticInitStep(dt, theta, sigma, pert)``
-in place of ``thetaInitStep``, with m fresh standard normals.  The projected stochastic model,
-AMS / TAMS / GPA, their score functions and CoupledThetaModel are not restated.
+in place of ``thetaInitStep``, with m fresh standard normals.
+
+``ProjectedThetaStepper`` and ``StochasticProjectedThetaStepper`` are the loop on
+``ProjectedThetaModel<Ocean>`` and ``StochasticProjectedThetaModel<Ocean>``
+(ProjectedThetaModel.H, StochasticProjectedThetaModel.H; TransientFactory.H:115-133 builds them
+when a "space" V is given, ``load_space`` reads it): the state is confined to x = V y and the
+stepper works on the small vector y.  A time step's Newton system is the k x k matrix
+V^T (J - B / dt / theta) V, factored once per step in the device library (csrc/projected.hip);
+no preconditioner is set up and no Krylov solver runs.  The model surface is
+
+    projSetState(y)                  state <- V y, small state <- y
+    projInitStep(dt, theta)          y_n, F_n, V^T B V, V^T J2 V and its factors
+    projStochasticInitStep(dt, theta, sigma, pert)
+    projNewtonStep() -> info         one Newton iteration on y; info.norm_dx = ||dy||_inf,
+                                     info.norm_f1 = ||r||_2 after the update
+    projRestore()                    state as at the init step
+    projRestrictState(), projGet("y")
+
+The theta = 0 branch of the reference's projected model is left out, as theta = 0 is
+everywhere here.  AMS / TAMS / GPA, their score functions and CoupledThetaModel are not restated.
 """
 from __future__ import annotations
 
@@ -136,6 +154,14 @@ class ThetaStepper:
         """The model call that starts a time step (ThetaModel::initStep), also after a rejected one."""
         self.model.thetaInitStep(self.dt, self.theta)
 
+    def _restore(self) -> None:
+        """AdaptiveTransient.H:107 after a failed Newton run"""
+        self.model.thetaRestore()
+
+    def _norm_x(self) -> float:
+        """||x|| of an accepted step, tdata.txt's column"""
+        return float(np.linalg.norm(self.model.getState()))
+
     def run(self) -> int:
         """AdaptiveTransient::run (AdaptiveTransient.H:88-171).  Returns 0, or 1 when a Newton
         run failed at the minimum time step or with adaptivity off."""
@@ -146,7 +172,7 @@ class ThetaStepper:
             self._init_step()
             self._newton()
             if not self.converged:
-                m.thetaRestore()
+                self._restore()
                 self.rejected.append(self.dt)
                 if self.dt == self.dt_min or not self.adaptive:
                     return 1
@@ -160,7 +186,7 @@ class ThetaStepper:
                 m.saveStateToFile(f"transient_{self.time:.8g}.h5")
             self.history.append(TransientRecord(
                 self.time * self.in_years, self.time_steps, self.dt * self.in_years,
-                float(np.linalg.norm(m.getState())), self.newton_steps, self.dt))
+                self._norm_x(), self.newton_steps, self.dt))
             if self.adaptive and self.newton_steps < self.min_wanted:
                 self.dt = min(self.dt * self.increase, self.dt_max)
             elif self.adaptive and self.newton_steps > self.max_wanted:
@@ -232,3 +258,113 @@ class StochasticThetaStepper(ThetaStepper):
     def _init_step(self) -> None:
         """StochasticThetaModel::initStep (StochasticThetaModel.H:52-72)"""
         self.model.stochasticInitStep(self.dt, self.theta, self.sigma, self._pert())
+
+
+class ProjectedThetaStepper(ThetaStepper):
+    """The time stepper on ProjectedThetaModel<Model> with the space V (N x k, 1 <= k <= 64, not
+    necessarily orthonormal): ``step(y, dt)`` is the time-step function ``get_time_step`` builds
+    (TransientFactory.H:55-67: setState, initStep, Newton::run on the small vector), and ``run()``
+    is ThetaStepper's loop with its parameters over it, from y = V^T state of the model's current
+    state.  ``y`` holds the small state; the history's norm_x is ||y||_2.  A rejected step puts
+    the model's state back (``projRestore``) and leaves y as it was."""
+
+    def __init__(self, model, V, params=None, **kw):
+        super().__init__(model, params, **kw)
+        V = np.asarray(V, dtype=np.float64)
+        if V.ndim != 2 or V.shape[1] < 1:
+            raise ValueError(f"{type(self).__name__}: V must be an N x k array, not of shape {V.shape} "
+                             "(the model says how many columns it takes: the device library 64)")
+        self.k = V.shape[1]
+        model.projSetBasis(V)
+        self.y = np.asarray(model.projRestrictState(), dtype=np.float64).copy()
+
+    def _proj_init(self) -> None:
+        self.model.projInitStep(self.dt, self.theta)
+
+    def _init_step(self) -> None:
+        """get_time_step's setState and initStep (TransientFactory.H:63-64)"""
+        self.model.projSetState(self.y)
+        self._proj_init()
+
+    def _newton(self) -> None:
+        """Newton::run (Newton.H:76-123) on the small vector of the initialised step"""
+        self.converged = False
+        self.normF = -1.0
+        self.newton_steps = 0
+        while self.newton_steps < self.max_newton:
+            info = self.model.projNewtonStep()
+            self.normdx, self.normF = float(info.norm_dx), float(info.norm_f1)
+            if self.normdx < self.tol and self.normF < self.tol:
+                self.converged = True
+                self.y = np.asarray(self.model.projGet("y"), dtype=np.float64).copy()
+                return
+            if self.normdx > 1e2:
+                return
+            self.newton_steps += 1
+
+    def _restore(self) -> None:
+        self.model.projRestore()
+
+    def _norm_x(self) -> float:
+        return float(np.linalg.norm(self.y))
+
+    def step(self, y, dt: float) -> np.ndarray:
+        """One time step of length dt from the small state y -> the new small state (Newton's
+        last iterate, converged or not: ``converged`` says which, as Newton::run returns x)."""
+        self.y = np.array(y, dtype=np.float64).reshape(-1)
+        if self.y.size != self.k:
+            raise ValueError(f"{type(self).__name__}: y has {self.y.size} entries, V has {self.k} columns")
+        self.dt = float(dt)
+        self._init_step()
+        self._newton()
+        if not self.converged:
+            self.y = np.asarray(self.model.projGet("y"), dtype=np.float64).copy()
+        return self.y.copy()
+
+
+class StochasticProjectedThetaStepper(ProjectedThetaStepper, StochasticThetaStepper):
+    """The same on StochasticProjectedThetaModel<Model>: every step starts with
+    ``projStochasticInitStep(dt, theta, sigma, pert)``.  "sigma", "noise seed", ``pert_source``, the
+    Philox blocks and ``draws`` are StochasticThetaStepper's, unchanged: a rejected step draws again."""
+
+    defaults = StochasticThetaStepper.defaults
+
+    def __init__(self, model, V, params=None, pert_source=None):
+        # ProjectedThetaStepper's constructor hands pert_source on to StochasticThetaStepper's
+        super().__init__(model, V, params, pert_source=pert_source)
+
+    def _proj_init(self) -> None:
+        """StochasticProjectedThetaModel::initStep (StochasticProjectedThetaModel.H:71-92)"""
+        self.model.projStochasticInitStep(self.dt, self.theta, self.sigma, self._pert())
+
+
+def load_space(path: str, nrows: int = None) -> np.ndarray:
+    """The "space" parameter's file (TransientFactory.H:177-196): a Matrix Market *array* file, as
+    ``EpetraExt::MatrixMarketFileToMultiVector`` reads it (real, general, column-major values, one
+    per line) -> an N x k array.  nrows, if given, is the model's row count, which N must equal.
+    A coordinate file, another field or symmetry, a size line that is not two positive integers
+    and a wrong number of values are refused by name."""
+    with open(path) as f:
+        head = f.readline().split()
+        if len(head) < 5 or head[0] != "%%MatrixMarket" or head[1].lower() != "matrix":
+            raise ValueError(f"load_space: {path} is not a Matrix Market matrix file")
+        fmt, field, sym = (h.lower() for h in head[2:5])
+        if fmt != "array":
+            raise ValueError(f'load_space: {path} is in "{fmt}" format; the space must be an "array" file')
+        if field not in ("real", "double", "integer") or sym != "general":
+            raise ValueError(f'load_space: {path} holds a "{field} {sym}" matrix; "real general" is needed')
+        line = f.readline()
+        while line and (line.startswith("%") or not line.strip()):
+            line = f.readline()
+        size = line.split()
+        if len(size) != 2 or not all(t.isdigit() for t in size) or int(size[0]) < 1 or int(size[1]) < 1:
+            raise ValueError(f"load_space: {path}: the size line {line.strip()!r} is not 'rows columns'")
+        n, k = int(size[0]), int(size[1])
+        if nrows is not None and n != int(nrows):
+            raise ValueError(f"load_space: {path} has {n} rows, the model has {int(nrows)}")
+        if k > 64:
+            raise ValueError(f"load_space: {path} has {k} columns, at most 64 are supported")
+        vals = np.array(f.read().split(), dtype=np.float64)
+    if vals.size != n * k:
+        raise ValueError(f"load_space: {path} holds {vals.size} values, its size line says {n} x {k}")
+    return np.ascontiguousarray(vals.reshape(k, n).T)

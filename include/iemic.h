@@ -46,10 +46,11 @@ extern "C" {
 /* Version of this header's structs and entry points.  Bumped whenever a struct changes
  * size or meaning (5: iemic_solve_info gained `safeguard` in round 4, the device vector
  * algebra of round 5; 7: surface fluxes and inserted forcing fields; 8: the theta time stepper;
- * 9: linear stability analysis; 10: the stochastic theta model); a caller built against another
+ * 9: linear stability analysis; 10: the stochastic theta model; 11: the projected theta model); a
+ * caller built against another
  * header must refuse to run:
  *   if (iemic_abi_version() != IEMIC_ABI_VERSION) abort(); */
-#define IEMIC_ABI_VERSION 10
+#define IEMIC_ABI_VERSION 11
 int iemic_abi_version(void);
 
 typedef struct iemic_ctx iemic_ctx;
@@ -437,6 +438,61 @@ int iemic_forcing_export(iemic_ctx* ctx, int64_t* rows, int* cols, double* vals,
  * before anything runs. */
 int iemic_theta_init_step_noise(iemic_ctx* ctx, double dt, double theta, double sigma, const double* pert);
 
+/* ---- the projected theta model (src/transient/ProjectedThetaModel.H and
+ * StochasticProjectedThetaModel.H; TransientFactory.H:115-133 builds them when a "space" V is
+ * given): the state is confined to x = V y, V an N x k basis, 1 <= k <= IEMIC_PROJ_MAX_K, which
+ * need not be orthonormal.  A time step's Newton system is the k x k matrix V^T J2 V, factored
+ * once per step on the host; no preconditioner is set up and no Krylov solver runs.  With
+ * y_n = V^T x_n, F_n = V^T F(x_n) and VMV = V^T B V of iemic_proj_init_step:
+ *   r(y) = dt (1 - theta) F_n + dt theta V^T F(V y) + VMV (y_n - y)  [+ G]
+ * The small vectors are host arrays of k doubles (k x k row-major for the matrices), the same on
+ * every rank.  Every call but set_basis / clear returns IEMIC_ESTATE, by name, before a basis is
+ * set; rhs, solve, newton_step and restore also before the first init step. */
+#define IEMIC_PROJ_MAX_K 64
+/* The constructor's V_ (ProjectedThetaModel.H:38-65): V is column-major, k columns of
+ * iemic_nrows doubles, each in the layout iemic_set_state takes.  The columns' halo rows are
+ * exchanged here, once.  The small state becomes V^T state (smallState_ = restrict(state)).
+ * k outside 1 .. IEMIC_PROJ_MAX_K, a null V and a non-finite entry are refused with IEMIC_EINVAL. */
+int iemic_proj_set_basis(iemic_ctx* ctx, const double* V, int k);
+int iemic_proj_clear(iemic_ctx* ctx);
+/* restrict (ProjectedThetaModel.H:196-206): y = V^T state */
+int iemic_proj_restrict_state(iemic_ctx* ctx, double* y);
+/* setState (ProjectedThetaModel.H:114-118): state = V y, small state = y */
+int iemic_proj_set_state(iemic_ctx* ctx, const double* y);
+/* initStep (ProjectedThetaModel.H:70-112) in its order: y_n = V^T state (the restriction of the
+ * large state, not the stored y: the two differ when V is not orthonormal), F_n = V^T F(state),
+ * VMV = V^T B V, J2 = J - B / dt / theta at the state (iemic_theta_jacobian's), VAV = V^T J2 V and
+ * its LU factors with partial pivoting.  Disarms the noise.  theta outside (0, 1] (the reference's
+ * theta = 0 branch, which factors VMV, is left out: VMV is singular whenever V reaches the W, P
+ * or land rows) and dt <= 0 are refused with IEMIC_EINVAL, a VAV with a zero or non-finite pivot
+ * with IEMIC_ERANGE, naming the pivot. */
+int iemic_proj_init_step(iemic_ctx* ctx, double dt, double theta);
+/* StochasticProjectedThetaModel::initStep (:71-92): iemic_proj_init_step, then
+ * G = V^T ((sqrt(dt) sigma) (B_f pert)), the restriction of iemic_theta_init_step_noise's field
+ * (the reference forms (B_f^T V)^T pert, the same product), armed until the next init step.  pert,
+ * sigma: iemic_theta_init_step_noise's rules.  The full model's noise is disarmed (the field is
+ * shared). */
+int iemic_proj_init_step_noise(iemic_ctx* ctx, double dt, double theta, double sigma, const double* pert);
+/* computeRHS (ProjectedThetaModel.H:125-155; with noise StochasticProjectedThetaModel.H:104-108):
+ * r at the current state and small state; r may be NULL */
+int iemic_proj_rhs(iemic_ctx* ctx, double* r);
+/* solve (ProjectedThetaModel.H:163-193): VAV dy = r / dt / theta with the step's factors */
+int iemic_proj_solve(iemic_ctx* ctx, const double* r, double* dy);
+/* One iteration of Newton.H:94-99 on the small state: dy from the current r (computed first when
+ * the state changed since the last one), y -= dy, state = V y, F, r. */
+typedef struct {
+    double norm_dx;              /* ||dy||_inf                                       */
+    double norm_f1;              /* ||r||_2 after the update                         */
+    double t_total_ms;
+} iemic_proj_info;
+int iemic_proj_newton_step(iemic_ctx* ctx, iemic_proj_info* info);
+/* AdaptiveTransient.H:107 after a failed Newton run: the state and the small state as they were at
+ * the init step, so iemic_proj_get("y") and iemic_proj_rhs agree with the state again */
+int iemic_proj_restore(iemic_ctx* ctx);
+/* the small quantities of the model, `what` one of "y", "y_n", "F_n", "r", "G" (k doubles) or
+ * "VMV", "VAV" (k x k, row-major); IEMIC_EINVAL for another name */
+int iemic_proj_get(iemic_ctx* ctx, const char* what, double* out);
+
 /* ---- linear stability of the state: J x = lambda B x by shift-invert Arnoldi -----------
  * The seam is the generalised eigenvalue solver the reference's drivers build on
  * applyMatrix / applyMassMat / applyPrecon (src/utils/JDQZInterface.H; run_ocean.C:82-97)
@@ -507,6 +563,9 @@ int iemic_eigs_end(iemic_ctx* ctx);
 /* ---- profiling helpers (bench): time n launches of the SpMV kernel with HIP events
  * on the stream it runs on; returns mean kernel milliseconds. */
 int iemic_time_spmv(iemic_ctx* ctx, int nrep, double* ms_per_launch);
+/* The block product W(:, b) = J V(:, b), b < k, alone (no halo exchange), in the manner of
+ * iemic_time_spmv: mean milliseconds of one product of k columns (copies of the state). */
+int iemic_time_spmm(iemic_ctx* ctx, int k, int nrep, double* ms_per_product);
 /* measurement helper (no reference counterpart): nrep back-to-back preconditioner applies
  * (iemic_prec_compute first) on the device, GPU ms per apply (events) and host ms per apply
  * spent enqueueing */
