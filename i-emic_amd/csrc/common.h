@@ -318,6 +318,17 @@ struct Projected {
     std::vector<double> G, r;        /* the step's noise V^T (B_f pert ...), the residual  */
 };
 
+/* The rare-event score function's reference states (score.hip; ScoreFunctions.C's sol1, sol2, nrm
+ * and dist_factor): device copies in the ext layout, kept from iemic_score_set to iemic_score_clear */
+struct Score {
+    int set = 0;
+    int var = -1;                    /* 0..5: the rows NUN cell + var; -1: every owned row   */
+    double nrm = 0.0;                /* ||sol1 - sol2||_v                                   */
+    double dist_factor = 0.5;        /* ||sol1 - sol3||_v / nrm, 0.5 without sol3           */
+    DevBuf<double> s1, s2;           /* sol1, sol2                                          */
+    DevBuf<double> part, res;        /* k_sqdist2's partials (2 GRAM_BLOCKS) and the two sums */
+};
+
 /* A shift-invert Arnoldi run (eigs.hip): the basis of (J - sigma B)^-1 B and its work vectors,
  * ext layout, allocated by eigs_begin and freed by eigs_end */
 struct Eigs {
@@ -410,6 +421,7 @@ struct iemic_ctx {
     int64_t frc_gen = 0;             /* counts compute_forcing: what Stoch::coF was made from */
     iemic::Eigs eg;
     iemic::Projected pj;
+    iemic::Score sc;
     iemic::Geo geo() const;
     iemic_ctx() = default;
     iemic_ctx(const iemic_ctx&) = delete;
@@ -689,6 +701,15 @@ int proj_rhs(iemic_ctx* c, double* r);
 int proj_solve(iemic_ctx* c, const double* r, double* dy);
 int proj_newton_step(iemic_ctx* c, iemic_proj_info* info);
 int proj_restore(iemic_ctx* c);
+/* score.hip: the score function's two distances in one pass */
+/* out2 = sum (x - a)^2, sum (x - b)^2 over the owned rows of variable var (-1: all of them), summed
+ * over the ranks; x, a, b ext vectors; deterministic (two stages, no atomics) */
+int score_sqdist2(iemic_ctx* c, int var, const double* x, const double* a, const double* b, double* out2);
+int score_set(iemic_ctx* c, const double* sol1, const double* sol2, const double* sol3, int var);
+int score_eval(iemic_ctx* c, const double* v, double* dist, double* d1, double* d2);
+int score_clear(iemic_ctx* c);
+/* out (k x k, row-major, host) = V^T diag(e_var) V of the projected model's basis (var -1: V^T V) */
+int proj_gram_vv(iemic_ctx* c, int var, double* out);
 /* prec.hip */
 int prec_compute(iemic_ctx* c, const iemic_krylov* opt);
 int prec_apply(iemic_ctx* c, const double* r, double* z);

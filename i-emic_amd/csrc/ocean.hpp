@@ -19,6 +19,7 @@
 #ifndef IEMIC_OCEAN_HPP
 #define IEMIC_OCEAN_HPP
 
+#include <array>
 #include <cmath>
 #include <map>
 #include <memory>
@@ -333,6 +334,41 @@ class Ocean {
         const size_t k = k_ ? k_ : 1;
         std::vector<double> out(what == "VMV" || what == "VAV" ? k * k : k);
         check(iemic_proj_get(ctx_, what.c_str(), out.data()), "projGet");
+        return out;
+    }
+
+    /* ---- the rare-event score function (ScoreFunctions.C): d1 = ||x - sol1||_v / nrm and d2 from
+     * one pass over x, sol1 and sol2; var = -1 the default score (all rows), var = 1 the ocean
+     * score (the v rows) --------------------------------------------------------------------- */
+    /* sol1, sol2, sol3 (empty: none, the distance factor is 0.5): nrows() doubles each */
+    void scoreSet(const std::vector<double>& sol1, const std::vector<double>& sol2, const std::vector<double>& sol3,
+                  int var = -1)
+    {
+        if (sol1.size() != N_ || sol2.size() != N_ || (!sol3.empty() && sol3.size() != N_))
+            throw std::runtime_error("scoreSet: sol1, sol2 and sol3 must have nrows() = " + std::to_string(N_) +
+                                     " entries");
+        check(iemic_score_set(ctx_, sol1.data(), sol2.data(), sol3.empty() ? nullptr : sol3.data(), var), "scoreSet");
+    }
+    /* {nrm, distance factor} */
+    std::array<double, 2> scoreGet()
+    {
+        std::array<double, 2> out{};
+        check(iemic_score_get(ctx_, &out[0], &out[1]), "scoreGet");
+        return out;
+    }
+    /* {dist, d1, d2} of the device vector v (iemic_vec_alloc), or of the resident state */
+    std::array<double, 3> score(const double* v = nullptr)
+    {
+        std::array<double, 3> out{};
+        check(iemic_score(ctx_, v, &out[0], &out[1], &out[2]), "score");
+        return out;
+    }
+    /* V^T V (var = -1) or V^T diag(e_var) V of the basis, k x k row-major */
+    std::vector<double> projGramVV(int var = -1)
+    {
+        const size_t k = k_ ? k_ : 1;
+        std::vector<double> out(k * k);
+        check(iemic_proj_gram_vv(ctx_, var, out.data()), "projGramVV");
         return out;
     }
 

@@ -165,6 +165,11 @@ int iemic_test_spmm_kb(iemic_ctx* ctx, int kbmax);
  * (its work space is used).  Summed over the ranks. */
 int iemic_test_gram(iemic_ctx* ctx, int ka, int kb, const double* V, const double* d, const double* W, double* G);
 
+/* out2 = sum (x - a)^2, sum (x - b)^2 over the owned rows of variable var (-1: all) by
+ * score_sqdist2 (score.hip): the two sums iemic_score takes its distances from.  x, a, b: host
+ * vectors in the reference order; x NULL: the resident state.  Summed over the ranks. */
+int iemic_test_sqdist2(iemic_ctx* ctx, int var, const double* x, const double* a, const double* b, double* out2);
+
 /* Measurement helper (one rank): GPU milliseconds per k x k Gram product of the set basis and its
  * scratch, results fetched, nrep each: by proj_gram (ms[0]), by k multi-dot pairs each fetched on
  * its own (ms[1]) and by the same k launch pairs with one fetch (ms[2]). */

@@ -584,6 +584,21 @@ extern "C" int iemic_test_gram(iemic_ctx* c, int ka, int kb, const double* V, co
     return proj_gram(c, vd.p + o.o, ld, ka, d ? dd.p + o.o : nullptr, wd.p + o.o, ld, kb, G);
 }
 
+extern "C" int iemic_test_sqdist2(iemic_ctx* c, int var, const double* x, const double* a, const double* b, double* out2)
+{
+    if (!c || !a || !b || !out2) return bad("null argument");
+    if (hipSetDevice(c->device) != hipSuccess) return IEMIC_EDEVICE;
+    StreamGuard guard{c};
+    const int64_t ld = c->sub.nerows();
+    DevBuf<double> xd, ad, bd;
+    if ((x && xd.alloc((size_t)ld)) || ad.alloc((size_t)ld) || bd.alloc((size_t)ld)) return IEMIC_ENOMEM;
+    int rc = x ? put_columns(c, x, 1, xd.p, ld) : 0;
+    if (!rc) rc = put_columns(c, a, 1, ad.p, ld);
+    if (!rc) rc = put_columns(c, b, 1, bd.p, ld);
+    if (rc) return rc;
+    return score_sqdist2(c, var, x ? xd.p : c->d_x.p, ad.p, bd.p, out2);
+}
+
 extern "C" int iemic_test_gram_cost(iemic_ctx* c, int k, int nrep, double* ms)
 {
     if (!c || !ms || nrep < 1) return bad("null argument");

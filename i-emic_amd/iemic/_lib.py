@@ -16,7 +16,7 @@ PKG_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(PKG_DIR, "lib", os.environ.get("IEMIC_LIB", "libiemic_amd.so"))
 
 IEMIC_ENODEV = -19
-ABI_VERSION = 11            # IEMIC_ABI_VERSION of include/iemic.h this binding mirrors
+ABI_VERSION = 12            # IEMIC_ABI_VERSION of include/iemic.h this binding mirrors
 IEMIC_ENOCONV = 1           # iemic_newton_step: applied, but the solve missed its tolerance
 
 
@@ -202,6 +202,11 @@ def lib():
         "iemic_proj_newton_step": (C.c_int, [vp, P(ProjInfo)]),
         "iemic_proj_restore": (C.c_int, [vp]),
         "iemic_proj_get": (C.c_int, [vp, C.c_char_p, PD]),
+        "iemic_score_set": (C.c_int, [vp, PD, PD, PD, C.c_int]),
+        "iemic_score_get": (C.c_int, [vp, PD, PD]),
+        "iemic_score": (C.c_int, [vp, vp, PD, PD, PD]),
+        "iemic_score_clear": (C.c_int, [vp]),
+        "iemic_proj_gram_vv": (C.c_int, [vp, C.c_int, PD]),
         "iemic_shifted_jacobian": (C.c_int, [vp, C.c_double]),
         "iemic_eigs_begin": (C.c_int, [vp, C.c_double, C.c_int, C.c_uint64, P(Krylov)]),
         "iemic_eigs_step": (C.c_int, [vp, P(Krylov), PD, P(EigsInfo)]),
@@ -294,6 +299,7 @@ EXPORTED = ("iemic_abi_version", "iemic_create", "iemic_create_dist", "iemic_com
             "iemic_proj_set_basis", "iemic_proj_clear", "iemic_proj_restrict_state", "iemic_proj_set_state",
             "iemic_proj_init_step", "iemic_proj_init_step_noise", "iemic_proj_rhs", "iemic_proj_solve",
             "iemic_proj_newton_step", "iemic_proj_restore", "iemic_proj_get", "iemic_time_spmm",
+            "iemic_score_set", "iemic_score_get", "iemic_score", "iemic_score_clear", "iemic_proj_gram_vv",
             "iemic_shifted_jacobian", "iemic_eigs_begin", "iemic_eigs_step", "iemic_eigs_ritz",
             "iemic_eigs_restart", "iemic_eigs_residual", "iemic_eigs_end", "iemic_vec_alloc", "iemic_vec_free",
             "iemic_vec_update", "iemic_vec_dot", "iemic_vec_norm_inf", "iemic_vec_from_ref",

@@ -14,7 +14,8 @@ format those files use:
   fixed string), fill value, data layout (contiguous or compact) and attribute messages.
 
 It reads the reference's own test/ocean/ocean_reference.h5 and writes files it reads back;
-the written layout follows the same conventions (one B-tree leaf per group, contiguous
+the written layout follows the same conventions (one level-0 B-tree node per group with one
+symbol node for up to 128 members and further full ones beyond, up to 4096; contiguous
 little-endian datasets).  Not a general HDF5 implementation: chunked/compressed data,
 dense (fractal-heap) groups and superblock versions > 0 are rejected loudly.
 """
@@ -311,17 +312,22 @@ class _Writer:
             heap_data += _pad8(nme.encode() + b"\x00")
         heap_seg = self.alloc(heap_data)
         heap = self.alloc(b"HEAP" + bytes([0, 0, 0, 0]) + struct.pack("<QQQ", len(heap_data), UNDEF, heap_seg))
-        if len(names) > 2 * LEAF_K:
-            raise H5Error(f"more than {2 * LEAF_K} members in one group")
-        ents = b""
-        for nme in names:
-            ents += struct.pack("<QQI4x16x", offs[nme], children[nme], 0)
-        ents += b"\x00" * (40 * (2 * LEAF_K - len(names)))      # full-size symbol node
-        snod = self.alloc(b"SNOD" + bytes([1, 0]) + struct.pack("<H", len(names)) + ents)
-        # one leaf: key0 (empty name), child, key1 (largest name); node sized for 2K children
-        last = offs[names[-1]] if names else 0
-        tree = (b"TREE" + bytes([0, 0]) + struct.pack("<H", 1) + struct.pack("<QQ", UNDEF, UNDEF) +
-                struct.pack("<QQQ", 0, snod, last))
+        if len(names) > 2 * LEAF_K * 2 * NODE_K:
+            raise H5Error(f"more than {2 * LEAF_K * 2 * NODE_K} members in one group")
+        # up to 2 LEAF_K members: one symbol node.  More (a rare-event restart file's "experiments"
+        # and "xlist" groups): full symbol nodes in name order under the one level-0 B-tree node,
+        # which has room for 2 NODE_K of them
+        leaves = [names[i:i + 2 * LEAF_K] for i in range(0, len(names), 2 * LEAF_K)] or [[]]
+        tree = b"TREE" + bytes([0, 0]) + struct.pack("<H", len(leaves)) + struct.pack("<QQ", UNDEF, UNDEF)
+        tree += struct.pack("<Q", 0)                            # key 0: the empty name
+        for leaf in leaves:
+            ents = b""
+            for nme in leaf:
+                ents += struct.pack("<QQI4x16x", offs[nme], children[nme], 0)
+            ents += b"\x00" * (40 * (2 * LEAF_K - len(leaf)))   # full-size symbol node
+            snod = self.alloc(b"SNOD" + bytes([1, 0]) + struct.pack("<H", len(leaf)) + ents)
+            # child, then its key: the largest name of the leaf
+            tree += struct.pack("<QQ", snod, offs[leaf[-1]] if leaf else 0)
         tree += b"\x00" * (24 + 8 * (2 * NODE_K + 1) + 8 * 2 * NODE_K - len(tree))
         btree = self.alloc(tree)
         hdr = self.header([(0x11, struct.pack("<QQ", btree, heap))])

@@ -816,6 +816,49 @@ class Ocean:
         check(lib().iemic_proj_get(self._h, what.encode(), ptr(out)), "iemic_proj_get")
         return out.reshape(k, k) if what in ("VMV", "VAV") else out
 
+    # ---- the rare-event score function (ScoreFunctions.C; driven by iemic.rare_event) -----
+    def scoreSet(self, sol1, sol2, sol3=None, var: int = -1) -> None:
+        """get_default_score_function (var = -1: all rows) / get_ocean_score_function (var = 1: the
+        v rows) up to the returned lambda: the device keeps sol1 and sol2, nrm = ||sol1 - sol2||_v
+        and the distance factor ||sol1 - sol3||_v / nrm (0.5 without sol3).  Vectors in setState's
+        layout.  sol1 = sol2 on the score's rows and a non-finite entry raise IemicError by name."""
+        vs = []
+        for name, s in (("sol1", sol1), ("sol2", sol2), ("sol3", sol3)):
+            if s is None and name == "sol3":
+                vs.append(None)
+                continue
+            s = np.ascontiguousarray(s, dtype=np.float64).reshape(-1)
+            if s.size != self.N:
+                raise IemicError(f"scoreSet: {name} has {s.size} entries, the model has {self.N} rows")
+            vs.append(s)
+        check(lib().iemic_score_set(self._h, ptr(vs[0]), ptr(vs[1]), None if vs[2] is None else ptr(vs[2]),
+                                    int(var)), "iemic_score_set")
+
+    def scoreGet(self):
+        """(nrm, distance factor) of the score function set."""
+        nrm, f = C.c_double(), C.c_double()
+        check(lib().iemic_score_get(self._h, C.byref(nrm), C.byref(f)), "iemic_score_get")
+        return nrm.value, f.value
+
+    def score(self, v: Optional[DeviceVec] = None):
+        """The returned lambda (ScoreFunctions.C:53-65, :163-189) on the device vector v, or on the
+        resident state: (dist, d1, d2), both distances from one pass over v, sol1 and sol2."""
+        dist, d1, d2 = C.c_double(), C.c_double(), C.c_double()
+        check(lib().iemic_score(self._h, None if v is None else v.p, C.byref(dist), C.byref(d1), C.byref(d2)),
+              "iemic_score")
+        return dist.value, d1.value, d2.value
+
+    def scoreClear(self) -> None:
+        check(lib().iemic_score_clear(self._h), "iemic_score_clear")
+
+    def projGramVV(self, var: int = -1) -> np.ndarray:
+        """V^T V (var = -1) or V^T diag(e_var) V of the basis (k x k): the matrix the projected
+        score functions take their norms with (ScoreFunctions.C:77, :204-213)."""
+        k = max(1, self._proj_k)
+        out = np.zeros(k * k)
+        check(lib().iemic_proj_gram_vv(self._h, int(var), ptr(out)), "iemic_proj_gram_vv")
+        return out.reshape(k, k)
+
     # ---- linear stability analysis (the JDQZInterface seam; iemic.eigs) -----------------
     def shiftedJacobian(self, sigma: float) -> None:
         """J - sigma B at the current state (J is assembled first); exportCSR, applyMatrix,

@@ -41,7 +41,8 @@ no preconditioner is set up and no Krylov solver runs.  The model surface is
     projRestrictState(), projGet("y")
 
 The theta = 0 branch of the reference's projected model is left out, as theta = 0 is
-everywhere here.  AMS / TAMS / GPA, their score functions and CoupledThetaModel are not restated.
+everywhere here.  The rare-event drivers over these steppers (naive Monte Carlo, GPA, AMS, TAMS) and
+their score functions are in ``iemic.rare_event``; CoupledThetaModel is not restated.
 """
 from __future__ import annotations
 
@@ -161,6 +162,24 @@ class ThetaStepper:
     def _norm_x(self) -> float:
         """||x|| of an accepted step, tdata.txt's column"""
         return float(np.linalg.norm(self.model.getState()))
+
+    def step(self, x, dt: float):
+        """One time step of length dt from the state x -> the new state: the time-step function
+        ``get_time_step`` builds (TransientFactory.H:55-67: setState, initStep, Newton::run), which
+        returns Newton's last iterate, converged or not (``converged`` says which).  x is a
+        ``DeviceVec`` of the model (the result is a new one; nothing goes through the host) or a
+        host vector (the result is one too).  Mirrors ``ProjectedThetaStepper.step``."""
+        m = self.model
+        host = isinstance(x, np.ndarray)
+        if host:
+            m.setState(x)
+        else:
+            m.vec_ops().set_state(x)
+        self.dt = float(dt)
+        m.preProcess()
+        self._init_step()
+        self._newton()
+        return m.getState().copy() if host else m.vec_ops().state()
 
     def run(self) -> int:
         """AdaptiveTransient::run (AdaptiveTransient.H:88-171).  Returns 0, or 1 when a Newton

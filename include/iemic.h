@@ -46,11 +46,12 @@ extern "C" {
 /* Version of this header's structs and entry points.  Bumped whenever a struct changes
  * size or meaning (5: iemic_solve_info gained `safeguard` in round 4, the device vector
  * algebra of round 5; 7: surface fluxes and inserted forcing fields; 8: the theta time stepper;
- * 9: linear stability analysis; 10: the stochastic theta model; 11: the projected theta model); a
+ * 9: linear stability analysis; 10: the stochastic theta model; 11: the projected theta model;
+ * 12: the rare-event score function); a
  * caller built against another
  * header must refuse to run:
  *   if (iemic_abi_version() != IEMIC_ABI_VERSION) abort(); */
-#define IEMIC_ABI_VERSION 11
+#define IEMIC_ABI_VERSION 12
 int iemic_abi_version(void);
 
 typedef struct iemic_ctx iemic_ctx;
@@ -492,6 +493,29 @@ int iemic_proj_restore(iemic_ctx* ctx);
 /* the small quantities of the model, `what` one of "y", "y_n", "F_n", "r", "G" (k doubles) or
  * "VMV", "VAV" (k x k, row-major); IEMIC_EINVAL for another name */
 int iemic_proj_get(iemic_ctx* ctx, const char* what, double* out);
+
+/* ---- the rare-event score function (src/transient/ScoreFunctions.C) ----------------------
+ * The AMS / TAMS / GPA drivers evaluate a score after every time step of every trajectory:
+ *   d1 = ||x - sol1||_v / nrm,  d2 = ||x - sol2||_v / nrm,  nrm = ||sol1 - sol2||_v,
+ *   dist = f - f exp(-1/2 (d1 / 0.25)^2) + (1 - f) exp(-1/2 (d2 / 0.25)^2),
+ * ||.||_v the 2-norm over the rows 6 cell + var of one variable (the ocean score: var = 1, v), or
+ * over all rows with var = -1 (the default score); land rows count.  Both sums of squares come out
+ * of one pass over x, sol1 and sol2, deterministically. */
+/* sol1, sol2, sol3: host vectors of iemic_nrows doubles in the reference's row order; sol3 may be
+ * NULL (f = 0.5), else f = ||sol1 - sol3||_v / nrm.  The context keeps device copies of sol1 and
+ * sol2.  IEMIC_EINVAL: a NULL or non-finite input, var outside -1 .. 5; IEMIC_ERANGE: nrm == 0.
+ * A refused call leaves no score function set. */
+int iemic_score_set(iemic_ctx* ctx, const double* sol1, const double* sol2, const double* sol3, int var);
+/* nrm and the distance factor f of the score function set (either may be NULL) */
+int iemic_score_get(iemic_ctx* ctx, double* nrm, double* dist_factor);
+/* the score of the device vector v (iemic_vec_alloc), or of the resident state with v = NULL;
+ * dist, d1, d2 may each be NULL.  IEMIC_ESTATE before iemic_score_set. */
+int iemic_score(iemic_ctx* ctx, const double* v, double* dist, double* d1, double* d2);
+int iemic_score_clear(iemic_ctx* ctx);
+/* out (k x k, row-major) = V^T V (var = -1) or V^T diag(e_var) V (var in 0 .. 5, e_var one on the
+ * rows of that variable) of the projected model's basis: what the projected score functions norm
+ * the small vectors with (ScoreFunctions.C:77, :204-213).  IEMIC_ESTATE without a basis. */
+int iemic_proj_gram_vv(iemic_ctx* ctx, int var, double* out);
 
 /* ---- linear stability of the state: J x = lambda B x by shift-invert Arnoldi -----------
  * The seam is the generalised eigenvalue solver the reference's drivers build on
